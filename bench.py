@@ -8,10 +8,19 @@ the RCCL gather of the 32-bit results to rank 0.  Default shard sizes
 runs config C4's per-GPU shard, 2 M x 1456 B per rank, so that N = 8 is exactly C4
 (16 M packets over 8 GPUs) and N = 2, 4 are the same per-rank work (weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` (N > 1) without torchrun starts N rank processes itself (one per GPU).
+
+A plain run does only what the headline figure needs: set up, settle() (the warmup), the
+K timed steps, --dump-outputs if given, the JSON line (value, ms_per_step, the roofline
+fraction from the timed region's own event pair).  Everything else described below (the
+instrumented pass, the read probe, the PMC traffic check, parity against the reference
+digests, the N = 1 extra legs and configs, cpu_baseline) runs only with --full.
+--dump-outputs DIR (rank 0) writes DIR/crc32.npy: the u32 result vector of the last timed
+step (the gathered one when N > 1) as float64, exact; above 2 M results a seeded sample of
+2 M of them, with the sampled indices in DIR/crc32_index.npy.
 
 Rank 0 prints ONE JSON line.  value = GiB/s of payload over all ranks (whole job, max
 time over ranks); the timed region holds nothing between the launches but the work, one
@@ -59,6 +68,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5, help="minimum untimed launches (see settle())")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the instrumented pass, the read probe, "
+                         "the PMC traffic check, parity against the reference digests, the N = 1 extra legs and "
+                         "configs, the CPU baseline (each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0: write the last timed step's result vector to DIR/crc32.npy (float64, exact u32 "
+                         "values; a seeded 2 M sample plus DIR/crc32_index.npy when it is larger)")
     ap.add_argument("--packets-per-rank", type=int, default=None,
                     help="default: 1 M at N = 1 (the metric), 2 M at N > 1 (config C4's shard; N = 8 is C4)")
     ap.add_argument("--cpu-seconds", type=float, default=3.0,
@@ -385,6 +401,29 @@ def parity_digest(vec_u32) -> dict:
             "vs": "reference crc32 over the same packets (tests/golden/bench_digests.json)" if want else "no digest"}
 
 
+DUMP_MAX = 2 << 20  # results written whole by --dump-outputs (float64: 16 MiB); above it a sample of as many
+
+
+def dump_outputs(d: str, vec_u32) -> dict:
+    """--dump-outputs: the result vector of the last timed step as d/crc32.npy, float64
+    (every u32 is exact in it).  More than DUMP_MAX results (N > 1: the gathered vector):
+    a sample of DUMP_MAX of them at sorted indices drawn once from SEED, the same for every
+    run of the same size, with the indices in d/crc32_index.npy."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    vec = np.ascontiguousarray(vec_u32).view(np.uint32)
+    info = {"dir": d, "results": int(vec.size), "files": ["crc32.npy"]}
+    if vec.size > DUMP_MAX:
+        idx = np.sort(np.random.default_rng(SEED).choice(vec.size, size=DUMP_MAX, replace=False))
+        np.save(os.path.join(d, "crc32_index.npy"), idx.astype(np.float64))
+        info["files"].append("crc32_index.npy")
+        info["sampled"] = DUMP_MAX
+        vec = vec[idx]
+    np.save(os.path.join(d, "crc32.npy"), vec.astype(np.float64))
+    return info
+
+
 def init_one_rank_group(local: int) -> None:
     """A one-rank RCCL world on this process's GPU (the --gather-n1 step, and the equal-work
     C4 shard leg of the N = 1 line): the N > 1 step's code path on one GPU."""
@@ -626,7 +665,7 @@ def rank_fields(kern_ms: list, gather_ms: list, el: float, steps: int, world: in
     pass; kern_ms = per-launch times from the instrumented pass.  Returns (max over ranks
     of el, fields):
       per_rank_kernel_ms, kernel_ms_max_over_ranks — mean CRC launch time per rank
-        (instrumented pass);
+        (instrumented pass; null when kern_ms is None: a run without --full has no such pass);
       per_rank_region_ms — the timed pass's CRC-stream time per step (its two events / K:
         the launches plus any stream wait for a result slot);
       per_rank_gather_ms, gather_ms_max_over_ranks — mean duration of a gather collective
@@ -645,8 +684,8 @@ def rank_fields(kern_ms: list, gather_ms: list, el: float, steps: int, world: in
     t = torch.tensor([el], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t.item())
-    km = sum(kern_ms) / len(kern_ms)
-    gm = sum(gather_ms) / len(gather_ms) if gather_ms else 0.0
+    km = sum(kern_ms) / len(kern_ms) if kern_ms else 0.0  # no instrumented pass (a run without --full): 0
+    gm =sum(gather_ms) / len(gather_ms) if gather_ms else 0.0
     rm = region_ms / steps if region_ms is not None else km
     mine = torch.tensor([km, gm, float(len(gather_ms)), rm], dtype=torch.float64, device=dev)
     allr = [torch.zeros(4, dtype=torch.float64, device=dev) for _ in range(world)]
@@ -656,7 +695,8 @@ def rank_fields(kern_ms: list, gather_ms: list, el: float, steps: int, world: in
     per_g = [round(r[1], 5) for r in rows]
     per_r = [round(r[3], 5) for r in rows]
     step_ms = round(el / steps * 1e3, 4)
-    return el, {"per_rank_kernel_ms": per_k, "kernel_ms_max_over_ranks": max(per_k),
+    return el, {"per_rank_kernel_ms": per_k if kern_ms else None,
+                "kernel_ms_max_over_ranks": max(per_k) if kern_ms else None,
                 "per_rank_region_ms": per_r,
                 "per_rank_gather_ms": per_g, "gather_ms_max_over_ranks": max(per_g),
                 "gathers_per_rank": [int(r[2]) for r in rows],
@@ -843,21 +883,28 @@ def main():
     kernel_name = W.LIB.wtp_last_kernel().decode()  # the instantiation the timed launches used
     gms = pipe.gather_ms()
     kmean = region_ms / args.steps  # average launch duration over the timed region (its two events)
-    # then as many steps again with an event pair around every launch (untimed diagnostics:
+    # what the timed path computed in its last step (rank 0: the gathered vector when N > 1)
+    vec = dumped = None
+    if rank == 0 and (args.full or args.dump_outputs):
+        import numpy as np
+        vec = (pipe.gathered_vector() if gathered is not None else pipe.last_out()).cpu().numpy().view(np.uint32)
+        if args.dump_outputs:
+            dumped = dump_outputs(args.dump_outputs, vec)
+    # --full: as many steps again with an event pair around every launch (untimed diagnostics:
     # the per-launch distribution, and the kernel time the N > 1 `overlap` is read against)
-    kern, _, _ = time_steps(pipe, args.steps, world, per_launch=True)
-    kern_ms = sorted(kern)
-    kmean_pl = sum(kern_ms) / len(kern_ms)
+    kern = None
+    if args.full:
+        kern, _, _ = time_steps(pipe, args.steps, world, per_launch=True)
+        kern_ms = sorted(kern)
+        kmean_pl = sum(kern_ms) / len(kern_ms)
 
     per_rank = None
     if world > 1 or args.gather_n1:  # --gather-n1: the same fields from a one-rank RCCL world
         el, per_rank = rank_fields(kern, gms, el, args.steps, world, dev, region_ms=region_ms)
 
-    # parity of the WHOLE result vector (rank 0: the gathered vector when N > 1)
+    # --full: parity of the WHOLE result vector
     parity = None
-    if rank == 0:
-        import numpy as np
-        vec = (pipe.gathered_vector() if gathered is not None else pipe.last_out()).cpu().numpy().view(np.uint32)
+    if rank == 0 and args.full:
         parity = parity_digest(vec)
         if parity["match"] is None:  # no reference digest for this size: oracle spot check
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -865,12 +912,12 @@ def main():
             parity["spot_check_vs_oracle"] = all(
                 int(vec[i]) == O.crc32(O.synth_fill_np(PAYLOAD, start_byte=i * PAYLOAD))
                 for i in (0, 1, len(vec) // 2, len(vec) - 1))
-    probe = read_probe(buf, nbytes, crc, stream, cus) if not args.no_probe else None
+    probe = read_probe(buf, nbytes, crc, stream, cus) if args.full and not args.no_probe else None
 
     total_bytes = float(nbytes) * world * args.steps
     value = total_bytes / el / 2**30
     achieved = nbytes / (kmean * 1e-3) / 1e9  # GB/s, algorithmic read bytes per launch
-    traffic, traffic_info = pmc_traffic(n, W.LIB_PATH)
+    traffic, traffic_info = pmc_traffic(n, W.LIB_PATH) if args.full else (None, {"status": "not checked (needs --full)"})
     line = {
         "metric": METRIC,
         "value": round(value, 2),
@@ -878,6 +925,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(el / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "weak",
@@ -906,10 +954,11 @@ def main():
                                            "kernel_ms_mean": round(kmean_pl, 5),
                                            "kernel_ms_median": round(kern_ms[len(kern_ms) // 2], 5),
                                            "kernel_ms_p10": round(kern_ms[len(kern_ms) // 10], 5),
-                                           "kernel_ms_p90": round(kern_ms[(9 * len(kern_ms)) // 10], 5)},
+                                           "kernel_ms_p90": round(kern_ms[(9 * len(kern_ms)) // 10], 5)}
+                                          if args.full else None,
                      "bytes_per_launch": nbytes,
                      "frac_of_same_box_read_probe": round(achieved / probe["GBs"], 4) if probe else None},
-        "kernel_us_instrumented_pass": [round(k * 1e3, 1) for k in kern],
+        "kernel_us_instrumented_pass": [round(k * 1e3, 1) for k in kern] if args.full else None,
         "warmup_run": warm_done,
         "warmup_rule": "max(--warmup, 100) launches, then until 3 consecutive 25-launch block means agree "
                        "within 1% (cap 3 s); untimed",
@@ -917,6 +966,7 @@ def main():
         "same_box_read_probe": probe,
         "pct_hbm_read_roofline": round(100 * achieved / HBM_PEAK_GBS, 2),
         "parity": parity,
+        "outputs": dumped,
     }
     if per_rank is not None:
         line.update(per_rank)
@@ -925,7 +975,7 @@ def main():
                                      "through host tensors. Exercises the --gpus N entry end to end; its timings "
                                      "are NOT a scaling measurement",
                              "backend": dist.get_backend()}
-    extras = rank == 0 and world == 1 and not args.gather_n1 and n == 1 << 20 and not args.no_extras
+    extras = args.full and rank == 0 and world == 1 and not args.gather_n1 and n == 1 << 20 and not args.no_extras
     if extras:  # after the timed region and the probe: neither leg touches the headline numbers
         run_extra_legs(line, parity, W, shard, buf, nbytes, n, dev, local, stream, args)
     if extras and not args.no_configs:  # every other BASELINE config, parity vs reference digests
@@ -935,7 +985,7 @@ def main():
         line["configs"] = config_legs.run(W, TimingEvent)
         if line["configs"]["parity_all"] is False:
             parity["configs"] = False
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         hc = host_cores()
         threads = args.cpu_threads or hc["threads"]
         line["cpu_baseline"] = cpu_baseline(65536, args.cpu_seconds, threads, hc)

@@ -355,3 +355,34 @@ def test_config_legs_parity_aggregation(monkeypatch):
     r = CL.run(None, None)
     assert r["parity_all"] is None and any("error" in x for x in r["rows"])
     assert CL.run(None, None, only="c2")["parity_checks"] == 1
+
+
+def test_full_and_dump_outputs_flags(monkeypatch):
+    """--full is off by default (a plain run times its steps and nothing else) and
+    --dump-outputs takes a directory."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "5"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 5
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float64 holds every u32 exactly; a vector above DUMP_MAX is sampled
+    at indices that depend only on its size, stored beside it."""
+    import bench
+    v = np.array([0, 1, 0xFFFFFFFF, 0xCBF43926, 0x80000001], np.uint32)
+    info = bench.dump_outputs(str(tmp_path / "a"), v.view(np.int32))
+    got = np.load(tmp_path / "a" / "crc32.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), v) and info["files"] == ["crc32.npy"]
+    monkeypatch.setattr(bench, "DUMP_MAX", 1000)
+    big = (np.arange(5000, dtype=np.uint64) * 2654435761 % (1 << 32)).astype(np.uint32)
+    for d in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / d), big)
+        assert info["sampled"] == 1000 and info["results"] == 5000
+    idx = np.load(tmp_path / "b" / "crc32_index.npy")
+    assert idx.size == 1000 and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "c" / "crc32_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "crc32.npy"), big[idx.astype(np.int64)].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "b" / "crc32.npy"), np.load(tmp_path / "c" / "crc32.npy"))

@@ -148,7 +148,7 @@ def test_bench_pipelined_gather_one_rank(W):
     import subprocess
     import sys
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gather-n1", "--steps", "5", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gather-n1", "--steps", "5", "--warmup", "5",
                         "--no-cpu-baseline", "--no-probe"], capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -169,7 +169,7 @@ def test_bench_c4_shard_gather_one_rank(W):
     import subprocess
     import sys
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gather-n1", "--packets-per-rank", "2097152",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gather-n1", "--packets-per-rank", "2097152",
                         "--steps", "5", "--warmup", "5", "--no-cpu-baseline", "--no-probe"],
                        capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -179,7 +179,7 @@ def test_bench_c4_shard_gather_one_rank(W):
 
 
 def test_bench_n1_line_carries_equal_work_c4_leg(W):
-    """The default N = 1 line (the driver's invocation, shortened): the metric's 1 M
+    """The N = 1 line with --full (shortened): the metric's 1 M
     packets, plus c4_shard_1gpu — rank 0's 2 M-packet C4 shard through the N > 1 pipelined
     step with a one-rank RCCL gather, its gathered vector equal to the reference's 2 M
     digest — and alt_buffer."""
@@ -187,7 +187,7 @@ def test_bench_n1_line_carries_equal_work_c4_leg(W):
     import subprocess
     import sys
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "5", "--warmup", "5",
                         "--no-cpu-baseline", "--no-probe"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -232,7 +232,7 @@ def test_bench_rehearse_gpus2_end_to_end(W, gpus):
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--rehearse-one-gpu",
-                        "--steps", "3"], capture_output=True, text=True, timeout=300, env=env)
+                        "--full", "--steps", "3"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert line["n_gpus"] == gpus and line["rehearsal"]["backend"] == "gloo"
@@ -244,3 +244,33 @@ def test_bench_rehearse_gpus2_end_to_end(W, gpus):
     assert all(v > 0 for v in line["per_rank_kernel_ms"]) and all(v > 0 for v in line["per_rank_gather_ms"])
     assert abs(line["overlap"] - (line["step_ms"] - max(line["per_rank_region_ms"]))) < 1e-4
     assert line["value"] > 0 and line["steps"] == 3
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(W, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` run times its K steps and nothing
+    else: the line carries the headline fields and ms_per_step, none of the --full legs;
+    --dump-outputs writes the last timed step's CRC vector, element-wise the oracle's."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    n = 100_003
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "5",
+                        "--packets-per-rank", str(n), "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 7 and line["full"] is False and line["unit"] == "GiB/s" and line["dtype"] == "u8"
+    assert line["higher_is_better"] is True and line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] - n * PAYLOAD / (line["ms_per_step"] * 1e-3) / 2**30) <= 0.01 * line["value"]
+    for k in ("configs", "c4_shard_1gpu", "alt_buffer", "cpu_baseline"):
+        assert k not in line, k
+    assert line["parity"] is None and line["same_box_read_probe"] is None
+    assert line["roofline"]["instrumented_pass"] is None and line["roofline"]["traffic"] is None
+    assert line["roofline"]["kernel_ms_mean"] > 0
+    got = np.load(tmp_path / "out" / "crc32.npy")
+    assert got.dtype == np.float64 and line["outputs"]["files"] == ["crc32.npy"]
+    want = O.batch_fixed(O.synth_fill_np(n * PAYLOAD), PAYLOAD, PAYLOAD, n, threads=THREADS)
+    assert np.array_equal(got, want.astype(np.float64))

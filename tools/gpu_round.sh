@@ -29,7 +29,7 @@ run() {  # run <name> <seconds> <cmd...>
 
 pmc_refresh() {  # FETCH_SIZE pass over the bench -> gpurun_out/$TAG/pmc_traffic.json and profiles/pmc_traffic.json
   cd /tmp && run pmc 400 rocprofv3 --pmc FETCH_SIZE --output-format csv \
-    -d "$OUT/pmc" -o bench -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-probe --no-extras
+    -d "$OUT/pmc" -o bench -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-probe --no-extras
   cd "$ROOT"
   python3 tools/pmc_traffic.py $(find "$OUT/pmc" -name "*counter_collection.csv" | head -1) "$OUT/pmc_traffic.json" 1048576 \
     > "$OUT/pmc_traffic.log" 2>&1 && cp "$OUT/pmc_traffic.json" profiles/pmc_traffic.json
@@ -76,16 +76,16 @@ for s in $STEPS; do
              pmc_refresh
            fi
            run gpu_tests 900 python -u -m pytest tests -m gpu -v -rf --timeout=300 --timeout-method thread ;;
-    bench) run bench 400 python bench.py --steps 20 --warmup 5 ;;        # the driver's invocation
-    bench2) run bench2 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline ;;
-    bench200) run bench200 400 python bench.py --no-cpu-baseline ;;
-    c4shard) run c4shard 400 python bench.py --steps 20 --warmup 5 --packets-per-rank 2097152 --no-cpu-baseline ;;
-    c4gather) run c4gather 400 python bench.py --steps 20 --warmup 5 --gather-n1 --packets-per-rank 2097152 --no-cpu-baseline ;;
+    bench) run bench 400 python bench.py --full --steps 20 --warmup 5 ;;  # every leg of the line
+    bench2) run bench2 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline ;;
+    bench200) run bench200 400 python bench.py --full --no-cpu-baseline ;;
+    c4shard) run c4shard 400 python bench.py --full --steps 20 --warmup 5 --packets-per-rank 2097152 --no-cpu-baseline ;;
+    c4gather) run c4gather 400 python bench.py --full --steps 20 --warmup 5 --gather-n1 --packets-per-rank 2097152 --no-cpu-baseline ;;
     prof)  cd /tmp && run prof 400 rocprofv3 --kernel-trace --stats --output-format csv \
-             -d "$OUT/prof" -o bench -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu-baseline
+             -d "$OUT/prof" -o bench -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline
            cd "$ROOT" ;;
     profnox) cd /tmp && run profnox 400 rocprofv3 --kernel-trace --stats --output-format csv \
-             -d "$OUT/profnox" -o bench -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-extras
+             -d "$OUT/profnox" -o bench -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras
            cd "$ROOT" ;;
     pmcnew) pmc_refresh ;;
     pmccfg) # FETCH_SIZE and WRITE_SIZE of every configs-leg kernel, one config per process and pass
@@ -100,15 +100,15 @@ for s in $STEPS; do
            python3 tools/pmc_configs.py --summarize "$OUT/pmc_configs.json" $(for row in c2 c5_1.1 c5_1.0 verify build; do echo "$row=$OUT/pmccfg/$row"; done) \
              > "$OUT/pmc_configs.log" 2>&1 || true ;;
     c4ab)  run c4ab 600 python -u tools/c4_leg_ab.py --rounds ${C4AB_ROUNDS:-8} --steps 20 --out "$OUT/c4_leg_ab.json" ;;
-    rehearse) run rehearse 400 python bench.py --gpus 2 --rehearse-one-gpu --steps 20 --warmup 5 ;;
+    rehearse) run rehearse 400 python bench.py --full --gpus 2 --rehearse-one-gpu --steps 20 --warmup 5 ;;
     newtests) run gpu_tests_new 600 python -u -m pytest tests -m gpu -v -rf --timeout=300 --timeout-method thread \
              -k "rehearse or captured_on_torch or piece_ranges or equal_work_c4_leg or pipelined_gather_one_rank" ;;
     gev)   for k in ${GEV:-1 2 4}; do
-             run "c4gather_k$k" 300 python bench.py --steps 20 --warmup 5 --gather-n1 --packets-per-rank 2097152 --gather-every $k --no-cpu-baseline --no-probe
+             run "c4gather_k$k" 300 python bench.py --full --steps 20 --warmup 5 --gather-n1 --packets-per-rank 2097152 --gather-every $k --no-cpu-baseline --no-probe
            done ;;
     transient) run transient 200 python -u tools/transient.py --out "$OUT/transient.json" ;;
     pmc)   cd /tmp && run pmc 400 rocprofv3 --pmc FETCH_SIZE --output-format csv \
-             -d "$OUT/pmc" -o bench -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-probe
+             -d "$OUT/pmc" -o bench -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-probe
            cd "$ROOT" ;;
     profcfg) cd /tmp && run profcfg 600 rocprofv3 --kernel-trace --stats --output-format csv \
              -d "$OUT/profcfg" -o cfg -- python3 "$ROOT/tools/bench_configs.py" --only "${CFG_ONLY:-c2,c5,verify}" --out "$OUT/profcfg_configs.json"
