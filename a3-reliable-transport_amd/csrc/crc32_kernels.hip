@@ -2696,6 +2696,9 @@ int wtp_set_error_(int code, const char *msg) {
     return code;
 }
 
+// wtp_last_kernel() for launchers in other translation units (wtp_accept.hip)
+void wtp_set_kernel_(const char *name) { g_kernel = name ? name : ""; }
+
 int wtp_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;

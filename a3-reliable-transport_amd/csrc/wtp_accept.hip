@@ -1,0 +1,222 @@
+// wtp_accept.hip — device-side receive (include/wtp_crc32.h: wtp_accept_data_packets).
+//
+// The inverse of the fused builder: a batch of received datagrams in a device ring is
+// verified, window-checked, de-duplicated and its payloads are copied to their place in
+// the file image, with the cumulative ACK, in three stream-ordered launches and no host
+// synchronisation.  Semantics: the sequential arrival-order loop of the reference's
+// receiver (cpp/src/base/Receiver.cpp:25-35 memcpy into Packet1::data, :208-237 window
+// check, buffering, next_seq) and of wReceiver.cpp's pending.emplace (first arrival wins).
+//
+//   1. verify        wtp_crc32_verify_batch (the braided kernel on an aligned ring) -> ok[]
+//   2. k_accept_claim one lane per datagram: an intact in-window DATA datagram claims its
+//                    slot with atomicMin(&slot_len[s], 0x80000000 | i).  EMPTY (0xFFFFFFFF)
+//                    > any claim > any stored length (<= 1456), so a filled slot stays
+//                    filled and the lowest index wins; the window state itself is the
+//                    only scratch.
+//   3. k_accept_place 16 lanes per datagram: the owner (slot_len[s] == 0x80000000 | i)
+//                    copies its payload, then publishes slot_len[s] = len and place[i];
+//                    every lane also scans its share of slot_len for the first EMPTY slot
+//                    (the cumulative ACK).
+//
+// The copy is not fused into the CRC rounds (as BuildBEpi::kCopy is on the send side): it
+// would store payload bytes before the verdict, so a corrupt or duplicate datagram could
+// overwrite good data and tear a slot.  Only the owner of a slot ever writes it.
+//
+// A separate translation unit: k_fixed_braid and everything it inlines stay as they are
+// (tests/test_bench.py pins the headline kernel's machine code).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+
+#include "wtp_crc32.h"
+
+extern "C" int wtp_set_error_(int code, const char *msg);
+extern "C" void wtp_set_kernel_(const char *name);
+
+#ifndef WTP_ACCEPT_NT
+#define WTP_ACCEPT_NT 1  // the place kernel's 16-B payload stores stream (nt); A/B builds: 0
+#endif
+#ifndef WTP_ACCEPT_LNT
+#define WTP_ACCEPT_LNT 1  // the same for its 16-B ring loads
+#endif
+
+namespace wtp {
+namespace dev {
+
+typedef uint32_t au32x4 __attribute__((ext_vector_type(4)));
+
+constexpr uint32_t kClaim = 0x80000000u;  // claim of datagram i = kClaim | i (n < 2^31)
+constexpr uint32_t kGroup = 16;           // lanes per datagram in k_accept_place
+constexpr uint32_t kVecs = (WTP_MAX_PAYLOAD / 16 + kGroup - 1) / kGroup;  // 91 vectors -> 6 per lane
+
+__device__ __forceinline__ uint32_t be32(const uint8_t *p) {
+    return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | uint32_t(p[3]);
+}
+
+__device__ __forceinline__ au32x4 ld16(const au32x4 *p) {
+    return WTP_ACCEPT_LNT ? __builtin_nontemporal_load(p) : *p;
+}
+__device__ __forceinline__ void st16(au32x4 *p, au32x4 v) {
+    if (WTP_ACCEPT_NT)
+        __builtin_nontemporal_store(v, p);
+    else
+        *p = v;
+}
+
+// Slot of datagram i if it may be placed (intact, DATA, payload <= 1456 B, inside the
+// window), else WTP_NOT_PLACED.  ok[i] != 0 already says 16 <= recv_len <= stride.
+__device__ __forceinline__ uint32_t accept_slot(const uint8_t *__restrict__ ring, uint64_t stride,
+                                                const uint32_t *__restrict__ recv_len, const uint8_t *__restrict__ ok,
+                                                uint64_t i, uint32_t seq0, uint32_t window, uint32_t &len) {
+    const uint8_t good = ok[i];
+    const uint32_t rl = recv_len[i];
+    if (!good) return WTP_NOT_PLACED;  // the header is read only where verify saw >= 16 bytes
+    const uint8_t *h = ring + i * stride;
+    const uint32_t type = be32(h), seq = be32(h + 4);  // the compiler merges these into one 8-B load
+    len = rl - WTP_HEADER_BYTES;
+    const uint32_t s = seq - seq0;  // unsigned: wrap is well defined
+    return len <= WTP_MAX_PAYLOAD && type == WTP_TYPE_DATA && s < window ? s : WTP_NOT_PLACED;
+}
+
+// The ACK is kept as seq0 + (lowest EMPTY slot seen so far); "lower" is taken on the slot
+// index, i.e. after subtracting seq0, so a window that wraps 2^32 orders correctly.
+__device__ __forceinline__ void ack_lower(uint32_t *ack, uint32_t seq0, uint32_t s) {
+    uint32_t cur = __hip_atomic_load(ack, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (s < cur - seq0) {
+        const uint32_t seen = atomicCAS(ack, cur, seq0 + s);
+        if (seen == cur) break;
+        cur = seen;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_accept_claim(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t *__restrict__ recv_len,
+               const uint8_t *__restrict__ ok, uint64_t n, uint32_t seq0, uint32_t window, uint32_t *slot_len,
+               uint32_t *ack) {
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i == 0 && ack) *ack = seq0 + window;  // "no EMPTY slot": k_accept_place lowers it
+    if (i >= n) return;
+    uint32_t len = 0;
+    const uint32_t s = accept_slot(ring, stride, recv_len, ok, i, seq0, window, len);
+    if (s != WTP_NOT_PLACED) atomicMin(&slot_len[s], kClaim | uint32_t(i));
+}
+
+__global__ void __launch_bounds__(256)
+k_accept_place(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t *__restrict__ recv_len,
+               const uint8_t *__restrict__ ok, uint64_t n, uint32_t seq0, uint32_t window, uint8_t *__restrict__ out,
+               uint32_t *slot_len, uint32_t *__restrict__ place, uint32_t *ack) {
+    const uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    // Cumulative ACK: the first EMPTY slot.  Every claim made by k_accept_claim is placed
+    // below, so a claimed slot counts as filled whether or not its length is published
+    // yet.  A lane walks its slots in rising order and stops at its first EMPTY one.
+    if (ack) {
+        const uint64_t step = uint64_t(gridDim.x) * blockDim.x;
+        for (uint64_t s = t; s < window; s += step)
+            if (__hip_atomic_load(&slot_len[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == WTP_SLOT_EMPTY) {
+                ack_lower(ack, seq0, uint32_t(s));
+                break;
+            }
+    }
+    const uint64_t i = t / kGroup;
+    const uint32_t g = uint32_t(t % kGroup);
+    if (i >= n) return;
+    uint32_t len = 0;
+    uint32_t s = accept_slot(ring, stride, recv_len, ok, i, seq0, window, len);
+    // the owner's claim is still in the slot: only this group publishes over it, and it
+    // does so after this load (the 16 lanes of a group share a wave)
+    if (s != WTP_NOT_PLACED && slot_len[s] != (kClaim | uint32_t(i))) s = WTP_NOT_PLACED;
+    if (s == WTP_NOT_PLACED) {
+        if (place && g == 0) place[i] = WTP_NOT_PLACED;
+        return;
+    }
+    const uint8_t *src = ring + i * stride + WTP_HEADER_BYTES;
+    uint8_t *dst = out + uint64_t(s) * WTP_MAX_PAYLOAD;
+    if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0) {
+        const au32x4 *vs = reinterpret_cast<const au32x4 *>(src);
+        au32x4 *vd = reinterpret_cast<au32x4 *>(dst);
+        const uint32_t nvec = len / 16;
+        if (len == WTP_MAX_PAYLOAD) {
+            // a full packet, 91 vectors: rows 0 .. 4 whole, row 5 lanes 0 .. 10; all of a
+            // lane's loads are in flight before its first store
+            au32x4 w[kVecs];
+#pragma unroll
+            for (uint32_t k = 0; k + 1 < kVecs; ++k) w[k] = ld16(vs + g + k * kGroup);
+            const bool last = g + (kVecs - 1) * kGroup < WTP_MAX_PAYLOAD / 16;
+            if (last) w[kVecs - 1] = ld16(vs + g + (kVecs - 1) * kGroup);
+#pragma unroll
+            for (uint32_t k = 0; k + 1 < kVecs; ++k) st16(vd + g + k * kGroup, w[k]);
+            if (last) st16(vd + g + (kVecs - 1) * kGroup, w[kVecs - 1]);
+        } else {
+#pragma clang loop unroll_count(2)
+            for (uint32_t v = g; v < nvec; v += kGroup) st16(vd + v, ld16(vs + v));
+        }
+        const uint32_t b = nvec * 16 + g;  // byte-exact tail: at most 15 bytes, one per lane
+        if (b < len) dst[b] = src[b];
+    } else {
+        // any other alignment: bytes (exact; no access wider than the buffers' alignment)
+#pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
+        for (uint32_t b = g; b < len; b += kGroup) dst[b] = src[b];
+    }
+    if (g == 0) {
+        slot_len[s] = len;
+        if (place) place[i] = s;
+    }
+}
+
+}  // namespace dev
+}  // namespace wtp
+
+namespace {
+
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+int fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return wtp_set_error_(code, buf);
+}
+
+int launch_check(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(WTP_EHIP, "launch %s: %s", what, hipGetErrorString(e));
+    return WTP_OK;
+}
+
+}  // namespace
+
+extern "C" int wtp_accept_data_packets(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len, size_t n,
+                                       uint32_t seq0, uint32_t window, void *d_out, uint32_t *d_slot_len,
+                                       uint8_t *d_ok, uint32_t *d_place, uint32_t *d_ack, void *stream) {
+    using namespace wtp;
+    if (n >= (size_t(1) << 31)) return fail(WTP_EINVAL, "n %zu >= 2^31", n);
+    if (n > 0) {
+        if (!d_dgrams || !d_recv_len || !d_ok || !d_out || !d_slot_len) return fail(WTP_EINVAL, "null pointer");
+        if (stride < 16) return fail(WTP_EINVAL, "stride %zu < 16", stride);
+    } else {
+        if (!d_ack) return WTP_OK;  // nothing to place, nothing to report
+        if (window > 0 && !d_slot_len) return fail(WTP_EINVAL, "null pointer");
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint8_t *ring = static_cast<const uint8_t *>(d_dgrams);
+    int rc = wtp_crc32_verify_batch(d_dgrams, stride, d_recv_len, n, d_ok, nullptr, stream);
+    if (rc) return rc;
+    {
+        const uint64_t blocks = std::max<uint64_t>(1, (uint64_t(n) + 255) / 256);
+        hipLaunchKernelGGL(dev::k_accept_claim, dim3(unsigned(blocks)), dim3(256), 0, st, ring, uint64_t(stride),
+                           d_recv_len, d_ok, uint64_t(n), seq0, window, d_slot_len, d_ack);
+        if ((rc = launch_check("k_accept_claim"))) return rc;
+    }
+    // one 16-lane group per datagram; at least enough lanes to scan a small window at once
+    const uint64_t scan = d_ack ? std::min<uint64_t>((uint64_t(window) + 255) / 256, 1024) : 0;
+    const uint64_t blocks = std::max<uint64_t>({1, (uint64_t(n) * dev::kGroup + 255) / 256, scan});
+    hipLaunchKernelGGL(dev::k_accept_place, dim3(unsigned(blocks)), dim3(256), 0, st, ring, uint64_t(stride),
+                       d_recv_len, d_ok, uint64_t(n), seq0, window, static_cast<uint8_t *>(d_out), d_slot_len, d_place,
+                       d_ack);
+    wtp_set_kernel_("k_accept_place");
+    return launch_check("k_accept_place");
+}

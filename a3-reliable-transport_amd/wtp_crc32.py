@@ -21,6 +21,8 @@ LIB_PATH = os.environ.get("WTP_LIB") or os.path.join(HERE, "lib", "libwtp_crc32.
 
 MAX_PAYLOAD = 1456
 MAX_KERNEL_LEN = 4096
+SLOT_EMPTY = 0xFFFFFFFF  # WTP_SLOT_EMPTY: d_slot_len of an empty window slot
+NOT_PLACED = 0xFFFFFFFF  # WTP_NOT_PLACED: d_place of a datagram that was not placed
 
 
 class WtpError(RuntimeError):
@@ -47,6 +49,7 @@ def _load() -> C.CDLL:
         "wtp_crc32_batch_packed": (i32, [vp, sz, vp, vp, sz, vp, vp]),
         "wtp_crc32_verify_batch": (i32, [vp, sz, vp, sz, vp, vp, vp]),
         "wtp_build_data_packets": (i32, [vp, sz, u32, vp, sz, vp, vp]),
+        "wtp_accept_data_packets": (i32, [vp, sz, vp, sz, u32, u32, vp, vp, vp, vp, vp, vp]),
         "wtp_crc32_host_batch_fixed": (i32, [vp, sz, sz, sz, vp]),
         "wtp_crc32_host_chunked": (i32, [vp, sz, sz, vp]),
         "wtp_crc32_host_chunked_multi": (i32, [vp, sz, sz, vp, vp, i32]),
@@ -66,6 +69,7 @@ def _load() -> C.CDLL:
 LIB = _load()
 EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_count", "wtp_init", "wtp_device_status", "wtp_reserve_cus", "wtp_crc32",
             "wtp_crc32_batch_fixed", "wtp_crc32_batch_var", "wtp_crc32_batch_packed", "wtp_crc32_verify_batch", "wtp_build_data_packets",
+            "wtp_accept_data_packets",
             "wtp_crc32_host_batch_fixed", "wtp_crc32_host_chunked", "wtp_crc32_host_chunked_multi", "wtp_crc32_host_verify",
             "wtp_host_build_data_packets", "wtp_host_alloc", "wtp_host_free", "wtp_synth_fill")
 
@@ -128,6 +132,16 @@ def build_data_packets(payloads, total_bytes: int, seq0: int, wire, wire_stride:
                        stream=None) -> None:
     _check(LIB.wtp_build_data_packets(_dptr(payloads), total_bytes, seq0, _dptr(wire), wire_stride,
                                       _dptr(wire_len), _stream(stream)), "wtp_build_data_packets")
+
+
+def accept_data_packets(dgrams, stride: int, recv_len, n: int, seq0: int, window: int, out, slot_len, ok,
+                        place=None, ack=None, stream=None) -> None:
+    """Device-side receive (wtp_accept_data_packets): verify, place into the window's file
+    image `out` (window * 1456 B) / `slot_len` (window x u32, SLOT_EMPTY = empty), and the
+    cumulative ACK into `ack` (1 x u32)."""
+    _check(LIB.wtp_accept_data_packets(_dptr(dgrams), stride, _dptr(recv_len), n, seq0 & 0xFFFFFFFF, window,
+                                       _dptr(out), _dptr(slot_len), _dptr(ok), _dptr(place), _dptr(ack),
+                                       _stream(stream)), "wtp_accept_data_packets")
 
 
 def synth_fill(out, start_byte: int = 0, seed: int = 0x5EED, nbytes: int | None = None, stream=None) -> None:

@@ -162,6 +162,38 @@ int wtp_build_data_packets(const void *d_payloads, size_t total_bytes, uint32_t 
                            void *d_wire, size_t wire_stride, uint32_t *d_wire_len,
                            void *stream);
 
+/* Device-side receive, the inverse of wtp_build_data_packets: verify, window-place and
+   ACK a batch of datagrams (cpp/src/base/Receiver.cpp:25-35 payload memcpy + :208-237
+   window check, buffering, next_seq).  Datagrams as in wtp_crc32_verify_batch.  The
+   caller owns the window state, which persists across calls: d_out, window * 1456 bytes,
+   the file image from chunk seq0 on (slot s = bytes [s*1456, (s+1)*1456)), and
+   d_slot_len[window], WTP_SLOT_EMPTY for an empty slot, else the payload length stored
+   in it (set it to 0xFF bytes once; shift or reset it when the window advances).
+   The result equals processing the datagrams one by one in index (arrival) order:
+   d_ok[i] is what wtp_crc32_verify_batch writes.  Datagram i is placed iff d_ok[i],
+   ntohl(type) == WTP_TYPE_DATA, len = recv_len - 16 <= WTP_MAX_PAYLOAD,
+   s = ntohl(seqNum) - seq0 (unsigned 32-bit, so a wrapping window is well defined)
+   < window, slot s was empty on entry and no placed datagram of a lower index carries
+   the same seqNum (first arrival wins).  Then d_out[s*1456 .. +len) = payload,
+   d_slot_len[s] = len (0 for an empty payload) and d_place[i] = s; otherwise d_place[i]
+   = WTP_NOT_PLACED.  Nothing else in d_out or d_slot_len changes: bytes [len, 1456) of
+   a placed slot, slots that receive nothing, and all of d_out for a corrupt datagram
+   stay as they were; a slot never mixes two datagrams' bytes.  *d_ack = seq0 + the number
+   of leading non-empty slots after the call (the cumulative ACK).  d_place and d_ack may
+   be NULL.  n == 0 and window == 0 are valid; with n == 0, *d_ack is still written from
+   the existing state.  n < 2^31.  Fast copy (16-B vectors): a 16-B aligned ring with
+   stride % 16 == 0 and a 16-B aligned d_out; other alignments are copied bytewise.
+   Stream-ordered launches (verify, claim, place) with no host synchronisation; the call
+   uses no memory besides the caller's buffers (slots are claimed in d_slot_len itself)
+   and keeps no state: graph captures, replays and concurrent calls on different windows
+   are independent. */
+#define WTP_SLOT_EMPTY 0xFFFFFFFFu
+#define WTP_NOT_PLACED 0xFFFFFFFFu
+int wtp_accept_data_packets(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len, size_t n,
+                            uint32_t seq0, uint32_t window,
+                            void *d_out, uint32_t *d_slot_len,
+                            uint8_t *d_ok, uint32_t *d_place, uint32_t *d_ack, void *stream);
+
 /* ---- host-memory wrappers (library-owned pinned staging, synchronous) -------------- */
 
 /* Like wtp_crc32_batch_fixed but payloads and results live in host memory. */
