@@ -1,7 +1,7 @@
 // wReceiver.cpp — WTP receiver, config C1 plumbing around the CRC path.
 //
 //   wReceiver -p <port> -w <window> -d <output-dir> -o <log> [--crc cpu|gpu] [--once]
-//             [--batch N]
+//             [--batch N] [--digest]
 //   wReceiver --bench <seconds> -p <port> [--crc cpu|gpu] [--batch N]
 //
 // Reference behaviour (README.md:98-127, cpp/src/base/Receiver.cpp): one connection at a
@@ -18,6 +18,10 @@
 // Deliberate differences from the reference: buffered
 // out-of-order packets are flushed in order, the file goes to -d (not the CWD), ACKs
 // are 16-byte datagrams.  --once exits after the first completed connection (tests).
+//
+// --digest prints `digest <bytes> <crc32, 8 hex digits>` of each stored file when its
+// connection ends: the fold (wtp_crc32_combine) of every DATA packet's verified checksum,
+// taken as the packet is flushed to the file; the file is not hashed again.
 //
 // Batched receive: datagrams arrive through recvmmsg into a pinned
 // ring of --batch slots (default: the window size), the whole batch is verified with one
@@ -148,7 +152,7 @@ int main(int argc, char **argv) {
         Args a(argc, argv, {{"-p", "port"}, {"--port", "port"}, {"-w", "window"}, {"--window-size", "window"},
                             {"-d", "dir"}, {"--output-dir", "dir"}, {"-o", "log"}, {"--output-log", "log"},
                             {"--crc", "crc"}, {"--once", "flag:once"}, {"--batch", "batch"},
-                            {"--bench", "bench"}});
+                            {"--bench", "bench"}, {"--digest", "flag:digest"}});
         const int port = std::stoi(a.get("port", "0"));
         const uint32_t window = uint32_t(std::stoi(a.get("window", "0")));
         const bool benchmode = a.has("bench");
@@ -177,6 +181,10 @@ int main(int argc, char **argv) {
         int file_no = 0;
         std::ofstream out;
         std::map<uint32_t, std::vector<uint8_t>> pending;  // out-of-order DATA
+        std::map<uint32_t, uint32_t> pending_crc;           // their verified checksums (--digest)
+        const bool digest = a.has("digest");
+        uint32_t file_crc = 0;
+        uint64_t file_bytes = 0;
 
         while (!done) {
             const size_t got = ring.receive(fd);
@@ -199,6 +207,9 @@ int main(int argc, char **argv) {
                         start_seq = h.seqNum;
                         expected = 0;
                         pending.clear();
+                        pending_crc.clear();
+                        file_crc = 0;
+                        file_bytes = 0;
                         out.open(a.get("dir") + "/FILE-" + std::to_string(file_no) + ".out",
                                  std::ios::binary | std::ios::trunc);
                     }
@@ -212,10 +223,17 @@ int main(int argc, char **argv) {
                     ack_seq = h.seqNum;
                 } else if (h.type == DATA) {
                     if (!open || h.seqNum >= expected + window) continue;  // outside the window: drop
-                    if (h.seqNum >= expected)
-                        pending.emplace(h.seqNum, std::vector<uint8_t>(buf + kHeaderBytes, buf + n));
+                    if (h.seqNum >= expected) {
+                        const bool first = pending.emplace(h.seqNum, std::vector<uint8_t>(buf + kHeaderBytes, buf + n)).second;
+                        if (digest && first) pending_crc[h.seqNum] = h.checksum;  // == crc32(payload): verified above
+                    }
                     for (auto it = pending.find(expected); it != pending.end(); it = pending.find(expected)) {
                         out.write(reinterpret_cast<const char *>(it->second.data()), std::streamsize(it->second.size()));
+                        if (digest) {
+                            file_crc = wtp_crc32_combine(file_crc, pending_crc[expected], it->second.size());
+                            file_bytes += it->second.size();
+                            pending_crc.erase(expected);
+                        }
                         pending.erase(it);
                         ++expected;
                     }
@@ -226,6 +244,10 @@ int main(int argc, char **argv) {
                 send_ack(fd, log, ack_seq, peer);
                 if (h.type == END) {
                     out.close();
+                    if (digest) {
+                        std::printf("digest %llu %08X\n", (unsigned long long)file_bytes, file_crc);
+                        std::fflush(stdout);
+                    }
                     open = false;
                     ++file_no;
                     if (a.has("once")) done = true;

@@ -1,6 +1,11 @@
 // wSender.cpp — WTP sender (go-back-N), config C1 plumbing around the CRC path.
 //
 //   wSender -h <ip> -p <port> -w <window> -i <input> -o <log> [--crc cpu|gpu] [--gpus N]
+//           [--digest]
+//
+// --digest prints `digest <bytes> <crc32, 8 hex digits>` of the whole file once the transfer
+// completes: the fold (wtp_crc32_combine) of the chunk CRCs already computed for the
+// headers, in order; the file is neither re-read nor re-hashed.
 //
 // Reference behaviour (mmheyer/a3-reliable-transport README.md:62-127, cpp/src/base/
 // Sender.cpp): START with a random seqNum until ACKed, DATA seqNums from 0 in chunks of
@@ -155,7 +160,8 @@ int main(int argc, char **argv) {
     try {
         Args a(argc, argv, {{"-h", "host"}, {"--hostname", "host"}, {"-p", "port"}, {"--port", "port"},
                             {"-w", "window"}, {"--window-size", "window"}, {"-i", "input"}, {"--input-file", "input"},
-                            {"-o", "log"}, {"--output-log", "log"}, {"--crc", "crc"}, {"--gpus", "gpus"}});
+                            {"-o", "log"}, {"--output-log", "log"}, {"--crc", "crc"}, {"--gpus", "gpus"},
+                            {"--digest", "flag:digest"}});
         const int port = std::stoi(a.get("port", "0"));
         const int window = std::stoi(a.get("window", "0"));
         if (port <= 0 || port > 65535 || window <= 0 || !a.has("host") || !a.has("input")) {
@@ -227,6 +233,15 @@ int main(int argc, char **argv) {
         ::close(c.fd);
         std::cout << "sent " << file.size() << " bytes in " << nchunks << " DATA packets (crc " << (crc.gpu() ? "gpu" : "cpu")
                   << ")\n";
+        if (a.has("digest")) {
+            uint32_t d = 0;
+            for (uint32_t i = 0; i < nchunks; ++i) {
+                const size_t off = size_t(i) * kMaxPayload;
+                const uint32_t sum = fused ? get_header(built->slot(i)).checksum : sums[i];
+                d = wtp_crc32_combine(d, sum, std::min(kMaxPayload, file.size() - off));
+            }
+            std::printf("digest %zu %08X\n", file.size(), d);
+        }
         return 0;
     } catch (const std::exception &e) {
         std::cerr << "wSender: " << e.what() << "\n";

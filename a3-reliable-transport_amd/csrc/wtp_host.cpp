@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "crc32_combine.hpp"
 #include "wtp_crc32.h"
 
 // Defined in crc32_kernels.hip: sets the per-thread message read by wtp_last_error().
@@ -239,6 +240,34 @@ int wtp_crc32_host_chunked(const void *h_buf, size_t nbytes, size_t chunk, uint3
     const size_t n = (nbytes + chunk - 1) / chunk;
     const size_t tail = nbytes - (n - 1) * chunk;
     return host_fixed_impl(h_buf, chunk, chunk, n, tail, h_out);
+}
+
+uint32_t wtp_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+    return wtp::gf::combine(crc_a, crc_b, len_b);
+}
+
+// The chunk CRCs through the pinned pipeline, then the host fold: every chunk but the last
+// has WTP_MAX_PAYLOAD bytes, so the fold is a Horner scheme in the one constant
+// x^(8 * 1456), applied as a 4 x 256 byte-table operator (4 lookups per chunk).
+int wtp_crc32_host_buffer(const void *h_buf, size_t nbytes, uint32_t *h_crc) {
+    using namespace wtp;
+    if (!h_crc) return hfail(WTP_EINVAL, "h_crc is null", hipSuccess);
+    if (nbytes > 0 && !h_buf) return hfail(WTP_EINVAL, "h_buf is null", hipSuccess);
+    *h_crc = 0;
+    if (nbytes == 0) return WTP_OK;
+    const size_t n = (nbytes + WTP_MAX_PAYLOAD - 1) / WTP_MAX_PAYLOAD;
+    std::vector<uint32_t> crcs(n);
+    int rc = wtp_crc32_host_chunked(h_buf, nbytes, WTP_MAX_PAYLOAD, crcs.data());
+    if (rc) return rc;
+    const uint32_t m = gf::xpow8(WTP_MAX_PAYLOAD);
+    std::vector<uint32_t> op(1024);
+    for (uint32_t k = 0; k < 4; ++k)
+        for (uint32_t b = 0; b < 256; ++b) op[256 * k + b] = gf::mul(b << (8 * k), m);
+    uint32_t d = 0;
+    for (size_t i = 0; i + 1 < n; ++i)
+        d = op[d & 255u] ^ op[256 + ((d >> 8) & 255u)] ^ op[512 + ((d >> 16) & 255u)] ^ op[768 + (d >> 24)] ^ crcs[i];
+    *h_crc = gf::combine(d, crcs[n - 1], nbytes - (n - 1) * WTP_MAX_PAYLOAD);
+    return WTP_OK;
 }
 
 static int host_verify_loop(Pipe *P, const uint8_t *h, bool pinned, size_t stride, const uint32_t *h_recv_len,

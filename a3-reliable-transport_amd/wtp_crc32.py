@@ -50,6 +50,12 @@ def _load() -> C.CDLL:
         "wtp_crc32_verify_batch": (i32, [vp, sz, vp, sz, vp, vp, vp]),
         "wtp_build_data_packets": (i32, [vp, sz, u32, vp, sz, vp, vp]),
         "wtp_accept_data_packets": (i32, [vp, sz, vp, sz, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "wtp_crc32_combine": (u32, [u32, u32, u64]),
+        "wtp_crc32_concat_work_bytes": (sz, [sz]),
+        "wtp_crc32_concat": (i32, [vp, vp, u64, u64, sz, vp, sz, vp, vp]),
+        "wtp_crc32_buffer_work_bytes": (sz, [sz]),
+        "wtp_crc32_buffer": (i32, [vp, sz, vp, sz, vp, vp]),
+        "wtp_crc32_host_buffer": (i32, [vp, sz, C.POINTER(u32)]),
         "wtp_crc32_host_batch_fixed": (i32, [vp, sz, sz, sz, vp]),
         "wtp_crc32_host_chunked": (i32, [vp, sz, sz, vp]),
         "wtp_crc32_host_chunked_multi": (i32, [vp, sz, sz, vp, vp, i32]),
@@ -70,6 +76,8 @@ LIB = _load()
 EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_count", "wtp_init", "wtp_device_status", "wtp_reserve_cus", "wtp_crc32",
             "wtp_crc32_batch_fixed", "wtp_crc32_batch_var", "wtp_crc32_batch_packed", "wtp_crc32_verify_batch", "wtp_build_data_packets",
             "wtp_accept_data_packets",
+            "wtp_crc32_combine", "wtp_crc32_concat_work_bytes", "wtp_crc32_concat", "wtp_crc32_buffer_work_bytes",
+            "wtp_crc32_buffer", "wtp_crc32_host_buffer",
             "wtp_crc32_host_batch_fixed", "wtp_crc32_host_chunked", "wtp_crc32_host_chunked_multi", "wtp_crc32_host_verify",
             "wtp_host_build_data_packets", "wtp_host_alloc", "wtp_host_free", "wtp_synth_fill")
 
@@ -144,6 +152,42 @@ def accept_data_packets(dgrams, stride: int, recv_len, n: int, seq0: int, window
                                        _stream(stream)), "wtp_accept_data_packets")
 
 
+# ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """crc32(A || B) from crc32(A), crc32(B), len(B) (zlib crc32_combine; host, no device)."""
+    return int(LIB.wtp_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, len_b))
+
+
+def concat_work_bytes(n: int) -> int:
+    return int(LIB.wtp_crc32_concat_work_bytes(n))
+
+
+def buffer_work_bytes(nbytes: int) -> int:
+    return int(LIB.wtp_crc32_buffer_work_bytes(nbytes))
+
+
+def _work(work, need: int):
+    """(pointer, size) of the caller's work tensor, or of a new torch byte tensor."""
+    if work is None:
+        import torch
+        work = torch.empty(need, dtype=torch.uint8, device="cuda")
+    return work, _dptr(work), work.numel() * work.element_size()
+
+
+def crc32_concat(crc, lens, n: int, out, length: int = 0, last_len: int = 0, work=None, stream=None) -> None:
+    """out[0] = CRC of the n payloads' concatenation from their CRCs `crc` (u32 tensor);
+    lens: u32 tensor of lengths, or None for `length` bytes each and `last_len` for the last."""
+    work, wp, wb = _work(work, concat_work_bytes(n))
+    _check(LIB.wtp_crc32_concat(_dptr(crc), _dptr(lens), length, last_len, n, wp, wb, _dptr(out), _stream(stream)),
+           "wtp_crc32_concat")
+
+
+def crc32_buffer(buf, nbytes: int, out, work=None, stream=None) -> None:
+    """out[0] = crc32(buf[0 .. nbytes)) of a device buffer of any size and alignment."""
+    work, wp, wb = _work(work, buffer_work_bytes(nbytes))
+    _check(LIB.wtp_crc32_buffer(_dptr(buf), nbytes, wp, wb, _dptr(out), _stream(stream)), "wtp_crc32_buffer")
+
+
 def synth_fill(out, start_byte: int = 0, seed: int = 0x5EED, nbytes: int | None = None, stream=None) -> None:
     nb = out.numel() * out.element_size() if nbytes is None else nbytes
     _check(LIB.wtp_synth_fill(_dptr(out), start_byte, nb, seed, _stream(stream)), "wtp_synth_fill")
@@ -176,6 +220,14 @@ def host_chunked(buf: np.ndarray, chunk: int = MAX_PAYLOAD, nbytes: int | None =
     out = np.zeros((nb + chunk - 1) // chunk, dtype=np.uint32)
     _check(LIB.wtp_crc32_host_chunked(_np_ptr(buf), nb, chunk, _np_ptr(out)), "host_chunked")
     return out
+
+
+def host_buffer(buf: np.ndarray, nbytes: int | None = None) -> int:
+    """crc32 of a host buffer (wtp_crc32_host_buffer: device chunk CRCs, host fold)."""
+    nb = buf.nbytes if nbytes is None else nbytes
+    crc = C.c_uint32(0)
+    _check(LIB.wtp_crc32_host_buffer(_np_ptr(buf), nb, C.byref(crc)), "host_buffer")
+    return int(crc.value)
 
 
 def host_chunked_multi(buf: np.ndarray, chunk: int = MAX_PAYLOAD, devices=None, nbytes: int | None = None) -> np.ndarray:

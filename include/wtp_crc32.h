@@ -194,7 +194,56 @@ int wtp_accept_data_packets(const void *d_dgrams, size_t stride, const uint32_t 
                             void *d_out, uint32_t *d_slot_len,
                             uint8_t *d_ok, uint32_t *d_place, uint32_t *d_ack, void *stream);
 
+/* ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------
+   The reference's crc32(buf, size) takes any size; these give it for device-resident data
+   of any size from the per-chunk CRCs, by zlib's crc32_combine identity
+   crc32(A || B) = crc32(A) * x^(8|B|) mod P ^ crc32(B).
+
+   Host: crc32(A || B) from crc32(A), crc32(B) and |B|.  Square and multiply,
+   O(log len_b); any uint64 len_b (x has order dividing 2^32 - 1, so len_b acts mod
+   2^32 - 1).  combine(c, 0, 0) == c and combine(0, c, len) == c, so a fold over chunks
+   starts from 0.  Thread-safe, touches no device. */
+uint32_t wtp_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
+/* Device: *d_out = CRC-32 of the concatenation of n payloads, in index order, from their
+   CRCs d_crc[0 .. n) (e.g. the checksums in the builder's headers, or d_crc_out of the
+   verify call) and their lengths; the payloads themselves are never read, so no
+   WTP_MAX_KERNEL_LEN limit and no status flag apply.  d_len != NULL: payload i has
+   d_len[i] bytes, any uint32 value (0 included).  d_len == NULL: payloads 0 .. n-2 have
+   `len` bytes and payload n-1 has `last_len` (the builder's chunking: len = 1456,
+   last_len = total - (n-1)*1456), any uint64 values.  n == 0 writes 0, the CRC of the
+   empty message (unlike the batch calls, and like *d_ack above, the one result is
+   always written).  d_out is one uint32_t and nothing beside it is written; d_crc and
+   d_len are only read.  d_work is the caller's scratch of at least
+   wtp_crc32_concat_work_bytes(n) bytes (<= 64 KiB for any n), 4-byte aligned: its
+   contents on entry are arbitrary (it need not be zeroed), on return unspecified.
+   work_bytes below that size, or a NULL d_work, d_out, or d_crc with n > 0, returns
+   WTP_EINVAL.  One or two stream-ordered launches, no host synchronisation, no
+   allocation, no state kept: graph captures on any stream, replays of one graph and
+   concurrent calls on different work buffers are independent.  wtp_last_kernel() names
+   "k_concat_fold" (d_len == NULL) or "k_concat_var". */
+size_t wtp_crc32_concat_work_bytes(size_t n);
+int wtp_crc32_concat(const uint32_t *d_crc, const uint32_t *d_len, uint64_t len, uint64_t last_len,
+                     size_t n, void *d_work, size_t work_bytes, uint32_t *d_out, void *stream);
+
+/* Device: *d_out = crc32(d_buf[0 .. nbytes)) for any nbytes (64-bit) and any base
+   alignment; nbytes == 0 writes 0.  The 16-B aligned interior runs through the braided
+   kernel of wtp_crc32_batch_fixed in 1456-B chunks (their CRCs go to d_work), the head
+   before the first 16-B boundary (<= 15 B) and the tail (< 1456 B) are hashed by two
+   extra workgroups of the fold, so a misaligned base costs no more than those.  d_buf is
+   only read.  d_work, work_bytes, d_out, launches and independence as for
+   wtp_crc32_concat, with wtp_crc32_buffer_work_bytes(nbytes) = the concat size + 4 bytes
+   per 1456-B chunk; the braided launch plus two more.  Call wtp_init before capturing. */
+size_t wtp_crc32_buffer_work_bytes(size_t nbytes);
+int wtp_crc32_buffer(const void *d_buf, size_t nbytes, void *d_work, size_t work_bytes,
+                     uint32_t *d_out, void *stream);
+
 /* ---- host-memory wrappers (library-owned pinned staging, synchronous) -------------- */
+
+/* Host memory: *h_crc = crc32(h_buf[0 .. nbytes)), 0 for nbytes == 0.  The chunk CRCs of
+   wtp_crc32_host_chunked (chunk = 1456) folded on the host with one constant-multiplier
+   operator, four table lookups per chunk. */
+int wtp_crc32_host_buffer(const void *h_buf, size_t nbytes, uint32_t *h_crc);
 
 /* Like wtp_crc32_batch_fixed but payloads and results live in host memory. */
 int wtp_crc32_host_batch_fixed(const void *h_payloads, size_t stride, size_t len, size_t n,
