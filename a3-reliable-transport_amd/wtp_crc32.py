@@ -23,6 +23,9 @@ MAX_PAYLOAD = 1456
 MAX_KERNEL_LEN = 4096
 SLOT_EMPTY = 0xFFFFFFFF  # WTP_SLOT_EMPTY: d_slot_len of an empty window slot
 NOT_PLACED = 0xFFFFFFFF  # WTP_NOT_PLACED: d_place of a datagram that was not placed
+ACK_SELECTIVE, ACK_CUMULATIVE = 0, 1  # WTP_ACK_*: mode of tx_ingest_acks
+RETX_ALL = 1                  # WTP_RETX_ALL: flags of tx_build_retransmit
+TX_MAX_INFLIGHT = 1 << 20     # WTP_TX_MAX_INFLIGHT
 
 
 class WtpError(RuntimeError):
@@ -50,6 +53,9 @@ def _load() -> C.CDLL:
         "wtp_crc32_verify_batch": (i32, [vp, sz, vp, sz, vp, vp, vp]),
         "wtp_build_data_packets": (i32, [vp, sz, u32, vp, sz, vp, vp]),
         "wtp_accept_data_packets": (i32, [vp, sz, vp, sz, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "wtp_tx_ingest_acks": (i32, [vp, sz, vp, sz, u32, u32, u32, vp, vp, vp, vp, vp]),
+        "wtp_tx_work_bytes": (sz, [u32, u32]),
+        "wtp_tx_build_retransmit": (i32, [vp, sz, u32, u32, vp, vp, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, sz, vp]),
         "wtp_crc32_combine": (u32, [u32, u32, u64]),
         "wtp_crc32_concat_work_bytes": (sz, [sz]),
         "wtp_crc32_concat": (i32, [vp, vp, u64, u64, sz, vp, sz, vp, vp]),
@@ -75,7 +81,7 @@ def _load() -> C.CDLL:
 LIB = _load()
 EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_count", "wtp_init", "wtp_device_status", "wtp_reserve_cus", "wtp_crc32",
             "wtp_crc32_batch_fixed", "wtp_crc32_batch_var", "wtp_crc32_batch_packed", "wtp_crc32_verify_batch", "wtp_build_data_packets",
-            "wtp_accept_data_packets",
+            "wtp_accept_data_packets", "wtp_tx_ingest_acks", "wtp_tx_work_bytes", "wtp_tx_build_retransmit",
             "wtp_crc32_combine", "wtp_crc32_concat_work_bytes", "wtp_crc32_concat", "wtp_crc32_buffer_work_bytes",
             "wtp_crc32_buffer", "wtp_crc32_host_buffer",
             "wtp_crc32_host_batch_fixed", "wtp_crc32_host_chunked", "wtp_crc32_host_chunked_multi", "wtp_crc32_host_verify",
@@ -150,6 +156,33 @@ def accept_data_packets(dgrams, stride: int, recv_len, n: int, seq0: int, window
     _check(LIB.wtp_accept_data_packets(_dptr(dgrams), stride, _dptr(recv_len), n, seq0 & 0xFFFFFFFF, window,
                                        _dptr(out), _dptr(slot_len), _dptr(ok), _dptr(place), _dptr(ack),
                                        _stream(stream)), "wtp_accept_data_packets")
+
+
+# ---- device-side sender window -------------------------------------------------------
+def tx_ingest_acks(dgrams, stride: int, recv_len, n: int, mode: int, seq0: int, inflight: int, acked, ok, hit=None,
+                   counts=None, stream=None) -> None:
+    """ACK ingest (wtp_tx_ingest_acks): marks `acked` (inflight x u32, 0 / 1); counts (2 x
+    u32) = (leading ACKed slots, slots newly ACKed)."""
+    _check(LIB.wtp_tx_ingest_acks(_dptr(dgrams), stride, _dptr(recv_len), n, mode, seq0 & 0xFFFFFFFF, inflight,
+                                  _dptr(acked), _dptr(ok), _dptr(hit), _dptr(counts), _stream(stream)),
+           "wtp_tx_ingest_acks")
+
+
+def tx_work_bytes(inflight: int, max_sel: int) -> int:
+    return int(LIB.wtp_tx_work_bytes(inflight, max_sel))
+
+
+def tx_build_retransmit(payloads, total_bytes: int, seq0: int, inflight: int, acked, sent_ms, now_ms: int,
+                        timeout_ms: int, flags: int, wire, wire_stride: int, max_sel: int, sel=None, wire_len=None,
+                        counts=None, work=None, stream=None) -> None:
+    """Select the due slots of the window (un-ACKed and timed out, or all un-ACKed with
+    RETX_ALL) and rebuild their DATA datagrams into `wire` (wtp_tx_build_retransmit);
+    counts (2 x u32) = (emitted, due)."""
+    work, wp, wb = _work(work, tx_work_bytes(inflight, max_sel))
+    _check(LIB.wtp_tx_build_retransmit(_dptr(payloads), total_bytes, seq0 & 0xFFFFFFFF, inflight, _dptr(acked),
+                                       _dptr(sent_ms), now_ms & 0xFFFFFFFF, timeout_ms, flags, _dptr(wire),
+                                       wire_stride, max_sel, _dptr(sel), _dptr(wire_len), _dptr(counts), wp, wb,
+                                       _stream(stream)), "wtp_tx_build_retransmit")
 
 
 # ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------

@@ -194,6 +194,82 @@ int wtp_accept_data_packets(const void *d_dgrams, size_t stride, const uint32_t 
                             void *d_out, uint32_t *d_slot_len,
                             uint8_t *d_ok, uint32_t *d_place, uint32_t *d_ack, void *stream);
 
+/* ---- device-side sender window: ACK ingest and selective retransmit ----------------
+   The mirror of wtp_accept_data_packets.  The caller owns the window state, which persists
+   across calls: slot s in [0, inflight) is the DATA packet with seqNum seq0 + s (unsigned
+   32-bit, so a wrapping window is well defined), d_acked[s] is 0 or 1, d_sent_ms[s] is the
+   caller's millisecond clock at that packet's last send (it wraps at 2^32).  d_payloads
+   points at the first byte of chunk seq0 and total_bytes is the number of file bytes from
+   there on: slot s holds min(1456, total_bytes - s*1456) bytes.  When the window advances
+   by a, the caller shifts d_acked and d_sent_ms by a and moves d_payloads, total_bytes and
+   seq0.  inflight <= WTP_TX_MAX_INFLIGHT.
+
+   wtp_tx_ingest_acks turns a batch of received datagrams (laid out as in
+   wtp_crc32_verify_batch) into window state.  d_ok[i] is what wtp_crc32_verify_batch
+   writes (for a plain 16-byte ACK: checksum == 0, decided without hashing; a longer
+   datagram is hashed exactly; a payload above WTP_MAX_KERNEL_LEN is not ok, as there,
+   but this call does not set the status flag).  WTP_ACK_SELECTIVE (cpp/src/opt/
+   Sender.cpp:130-139, Window.cpp:45-54): datagram i counts iff d_ok[i], ntohl(type) ==
+   WTP_TYPE_ACK and s = ntohl(seqNum) - seq0 < inflight; then d_acked[s] = 1 and d_hit[i]
+   = s.  WTP_ACK_CUMULATIVE (cpp/src/base/Sender.cpp:107-109): it counts iff ok, of type
+   ACK and a = ntohl(seqNum) - seq0 has 0 < a <= inflight; then d_hit[i] = a, and
+   d_acked[s] = 1 for every s < the largest a of the batch.  Every other datagram gets
+   d_hit[i] = WTP_NOT_PLACED.  d_counts[0] = the number of leading slots with d_acked != 0
+   after the call (the window advance, Window.cpp:66-75), d_counts[1] = the number of
+   slots that went 0 -> 1 in this call; nothing else in d_acked changes.  The result
+   equals processing the datagrams one by one in index order.  d_hit may be NULL.  n == 0
+   and inflight == 0 are valid: d_counts is still written from the existing state.
+   n >= 2^31, inflight > WTP_TX_MAX_INFLIGHT, an unknown mode, stride < 16 or a NULL
+   required pointer (d_counts; d_acked with inflight > 0; d_dgrams, d_recv_len, d_ok with
+   n > 0) returns WTP_EINVAL before any device is touched.  Stream-ordered (a memset of
+   d_counts, one lane per datagram, one pass over the window), no host
+   synchronisation; the call uses no memory besides the caller's buffers and keeps no
+   state: graph captures, replays and concurrent calls on different windows are
+   independent. */
+#define WTP_ACK_SELECTIVE  0u   /* opt/Sender.cpp:130-139: an ACK names the one packet it acknowledges */
+#define WTP_ACK_CUMULATIVE 1u   /* base/Sender.cpp:107-109: an ACK names the next expected packet */
+#define WTP_RETX_ALL       1u   /* flags: every un-ACKed slot is due, timers ignored (go-back-N) */
+#define WTP_TX_MAX_INFLIGHT (1u << 20)
+int wtp_tx_ingest_acks(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len, size_t n,
+                       uint32_t mode, uint32_t seq0, uint32_t inflight, uint32_t *d_acked,
+                       uint8_t *d_ok, uint32_t *d_hit, uint32_t *d_counts, void *stream);
+
+/* wtp_tx_build_retransmit selects the slots that are due and builds exactly those
+   datagrams again (cpp/src/opt/Sender.cpp:121-127, Packet.cpp:52-56; with WTP_RETX_ALL
+   cpp/src/base/Sender.cpp:101-105).  Slot s is due iff d_acked[s] == 0 and (flags &
+   WTP_RETX_ALL or (uint32_t)(now_ms - d_sent_ms[s]) > timeout_ms).  Due slots are taken in
+   rising slot order and the first min(due, max_sel) of them are emitted: entry k gets
+   d_sel[k] = s, d_wire[k*wire_stride ..) = htonl{type = 2, seq0 + s, len, crc32(payload)}
+   || payload, byte-identical to what wtp_build_data_packets writes for that chunk,
+   d_wire_len[k] = 16 + len, and d_sent_ms[s] = now_ms.  d_counts[0] = the number emitted,
+   d_counts[1] = the number due (a caller whose ring was too small calls again).  Entries
+   k >= d_counts[0] of d_wire, d_sel and d_wire_len and the timers of slots not emitted stay
+   as they were; d_acked and d_payloads are only read.  d_sel and d_wire_len may be NULL.
+   inflight == 0 and max_sel == 0 are valid: d_counts is still written.  WTP_EINVAL (before
+   any device is touched): wire_stride < 1472, inflight > WTP_TX_MAX_INFLIGHT (the
+   window's bytes stay below 2 GiB),
+   (inflight - 1) * 1456 >= total_bytes with inflight > 0, work_bytes <
+   wtp_tx_work_bytes(inflight, max_sel), a NULL d_counts or d_work, a NULL d_payloads,
+   d_acked or d_sent_ms with inflight > 0, a NULL d_wire with inflight and max_sel > 0.
+   d_work is the caller's scratch as for wtp_crc32_concat (any alignment, contents
+   arbitrary on entry, unspecified on return, no allocation by the library);
+   wtp_tx_work_bytes is monotone in both arguments and at most 64 KiB + 16 bytes per
+   max_sel entry.  Fast path (16-B vectors, each payload byte read once: the emit kernel
+   hashes what it copies): 16-B aligned d_payloads and d_wire with wire_stride % 16 == 0;
+   other alignments, and a chunk shorter than 1456 bytes, are copied and hashed bytewise,
+   exactly.  Stream-ordered launches (count, select, emit) with no host synchronisation:
+   d_counts[0] is never read on the host, grids are sized from max_sel.  The call reads no
+   library table, so it needs no wtp_init before a capture.  wtp_last_kernel() names
+   "k_tx_emit" (or "k_tx_select" when max_sel or inflight is 0 and nothing can be
+   emitted). */
+size_t wtp_tx_work_bytes(uint32_t inflight, uint32_t max_sel);
+int wtp_tx_build_retransmit(const void *d_payloads, size_t total_bytes, uint32_t seq0, uint32_t inflight,
+                            const uint32_t *d_acked, uint32_t *d_sent_ms, uint32_t now_ms,
+                            uint32_t timeout_ms, uint32_t flags,
+                            void *d_wire, size_t wire_stride, uint32_t max_sel,
+                            uint32_t *d_sel, uint32_t *d_wire_len, uint32_t *d_counts,
+                            void *d_work, size_t work_bytes, void *stream);
+
 /* ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------
    The reference's crc32(buf, size) takes any size; these give it for device-resident data
    of any size from the per-chunk CRCs, by zlib's crc32_combine identity
