@@ -26,6 +26,8 @@ NOT_PLACED = 0xFFFFFFFF  # WTP_NOT_PLACED: d_place of a datagram that was not pl
 ACK_SELECTIVE, ACK_CUMULATIVE = 0, 1  # WTP_ACK_*: mode of tx_ingest_acks
 RETX_ALL = 1                  # WTP_RETX_ALL: flags of tx_build_retransmit
 TX_MAX_INFLIGHT = 1 << 20     # WTP_TX_MAX_INFLIGHT
+RX_MAX_WINDOW = 1 << 20       # WTP_RX_MAX_WINDOW (cumulative mode of rx_build_acks)
+RX_MAX_BATCH = 1 << 24        # WTP_RX_MAX_BATCH
 
 
 class WtpError(RuntimeError):
@@ -56,6 +58,8 @@ def _load() -> C.CDLL:
         "wtp_tx_ingest_acks": (i32, [vp, sz, vp, sz, u32, u32, u32, vp, vp, vp, vp, vp]),
         "wtp_tx_work_bytes": (sz, [u32, u32]),
         "wtp_tx_build_retransmit": (i32, [vp, sz, u32, u32, vp, vp, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, sz, vp]),
+        "wtp_rx_ack_work_bytes": (sz, [sz, u32, u32]),
+        "wtp_rx_build_acks": (i32, [vp, sz, vp, sz, u32, u32, u32, vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, sz, vp]),
         "wtp_crc32_combine": (u32, [u32, u32, u64]),
         "wtp_crc32_concat_work_bytes": (sz, [sz]),
         "wtp_crc32_concat": (i32, [vp, vp, u64, u64, sz, vp, sz, vp, vp]),
@@ -82,6 +86,7 @@ LIB = _load()
 EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_count", "wtp_init", "wtp_device_status", "wtp_reserve_cus", "wtp_crc32",
             "wtp_crc32_batch_fixed", "wtp_crc32_batch_var", "wtp_crc32_batch_packed", "wtp_crc32_verify_batch", "wtp_build_data_packets",
             "wtp_accept_data_packets", "wtp_tx_ingest_acks", "wtp_tx_work_bytes", "wtp_tx_build_retransmit",
+            "wtp_rx_ack_work_bytes", "wtp_rx_build_acks",
             "wtp_crc32_combine", "wtp_crc32_concat_work_bytes", "wtp_crc32_concat", "wtp_crc32_buffer_work_bytes",
             "wtp_crc32_buffer", "wtp_crc32_host_buffer",
             "wtp_crc32_host_batch_fixed", "wtp_crc32_host_chunked", "wtp_crc32_host_chunked_multi", "wtp_crc32_host_verify",
@@ -183,6 +188,25 @@ def tx_build_retransmit(payloads, total_bytes: int, seq0: int, inflight: int, ac
                                        _dptr(sent_ms), now_ms & 0xFFFFFFFF, timeout_ms, flags, _dptr(wire),
                                        wire_stride, max_sel, _dptr(sel), _dptr(wire_len), _dptr(counts), wp, wb,
                                        _stream(stream)), "wtp_tx_build_retransmit")
+
+
+# ---- device-side ACK generation --------------------------------------------------------
+def rx_ack_work_bytes(n: int, window: int, mode: int) -> int:
+    return int(LIB.wtp_rx_ack_work_bytes(n, window, mode))
+
+
+def rx_build_acks(dgrams, stride: int, recv_len, n: int, mode: int, seq0: int, window: int, ok, place, slot_len,
+                  ack_wire, ack_stride: int, skip: int, max_acks: int, src=None, counts=None, work=None,
+                  stream=None) -> None:
+    """The ACK datagrams a receiver owes for a batch that accept_data_packets has processed
+    (wtp_rx_build_acks): `ok` / `place` are accept's outputs, `slot_len` the window after
+    it (both unused and may be None with ACK_SELECTIVE).  The eligible datagrams of rank
+    [skip, skip + max_acks) become 16-byte ACKs in `ack_wire` (ack_stride bytes apart) with
+    their datagram index in `src`; counts (2 x u32) = (emitted, eligible)."""
+    work, wp, wb = _work(work, rx_ack_work_bytes(n, window, mode))
+    _check(LIB.wtp_rx_build_acks(_dptr(dgrams), stride, _dptr(recv_len), n, mode, seq0 & 0xFFFFFFFF, window, _dptr(ok),
+                                 _dptr(place), _dptr(slot_len), _dptr(ack_wire), ack_stride, skip, max_acks,
+                                 _dptr(src), _dptr(counts), wp, wb, _stream(stream)), "wtp_rx_build_acks")
 
 
 # ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------

@@ -270,6 +270,74 @@ int wtp_tx_build_retransmit(const void *d_payloads, size_t total_bytes, uint32_t
                             uint32_t *d_sel, uint32_t *d_wire_len, uint32_t *d_counts,
                             void *d_work, size_t work_bytes, void *stream);
 
+/* ---- device-side ACK generation: the receiver's reply ring ---------------------------
+   The fourth call of the protocol loop: it follows wtp_accept_data_packets on the same
+   stream, takes the same batch (datagrams as in wtp_crc32_verify_batch), seq0 and window,
+   accept's outputs d_ok and d_place and the window state d_slot_len after that call, and
+   writes the ACK datagrams the receiver owes, ready for the sender's wtp_tx_ingest_acks.
+   The window is fixed for the batch, as in accept.  The result equals processing the
+   datagrams one by one in index order.
+
+   Eligibility, the same in both modes: datagram i is answered iff d_ok[i] != 0,
+   ntohl(type) == WTP_TYPE_DATA, recv_len[i] - 16 <= WTP_MAX_PAYLOAD and, with d =
+   ntohl(seqNum) - seq0 in unsigned 32-bit arithmetic, d < window or d >= 0x80000000.  The
+   second case is a packet below the window: its ACK was lost, the sender re-sent it after
+   the receiver had moved on, and it must be ACKed again or the sender never finishes
+   (cpp/src/opt/Receiver.cpp:211-237 and cpp/src/base/Receiver.cpp:206-237 answer every
+   intact datagram they do not drop; wReceiver.cpp answers below `expected`).  An intact
+   in-window datagram that accept did not place because its slot was already full (a
+   duplicate, or the loser of the first-wins race) is still answered.  A datagram at or
+   above seq0 + window, a corrupt one, a runt, a payload above 1456 bytes and a type other
+   than DATA are not.
+
+   The ACK's seqNum.  WTP_ACK_SELECTIVE (opt/Receiver.cpp:213,227): the datagram's own
+   seqNum; d_place and d_slot_len are not read and may be NULL.  WTP_ACK_CUMULATIVE
+   (base/Receiver.cpp:213-227; wReceiver.cpp `ack_seq = expected`): seq0 + lead_i, where
+   lead_i is the number of leading non-empty slots after datagrams 0 .. i have been
+   processed in order.  Every slot s of the window has a fill time: j, the lowest index
+   with d_place[j] == s, if there is one; else -1 if d_slot_len[s] != WTP_SLOT_EMPTY (it was
+   filled before the batch); else never.  lead_i is the length of the leading run of slots
+   with fill time <= i.  A d_place entry >= window counts as WTP_NOT_PLACED, so any input is
+   defined and nothing is indexed outside the window.  With accept's own outputs seq0 +
+   lead_(n-1) equals accept's *d_ack.  Datagrams below the window carry the running value
+   too.
+
+   Output.  The eligible datagrams are ranked in rising index (arrival) order; those with
+   rank r in [skip, skip + max_acks) are emitted as entry k = r - skip:
+   d_ack_wire[k*ack_stride .. +16) = htonl{type = 3, seqNum, length = 0, checksum = 0}
+   (crc32 of the empty payload is 0) and d_src[k] = i.  d_counts[0] = the number emitted,
+   d_counts[1] = the number eligible; a caller whose ring was too small calls again with
+   skip += max_acks.  Entries k >= d_counts[0] of d_ack_wire and d_src and bytes [16,
+   ack_stride) of every slot stay as they were; every input is only read.  d_src may be
+   NULL.  n == 0, window == 0 and max_acks == 0 are valid: d_counts is still written.
+
+   WTP_EINVAL (before any device is touched): n > WTP_RX_MAX_BATCH, window >
+   WTP_RX_MAX_WINDOW in cumulative mode, an unknown mode, stride < 16, ack_stride < 16,
+   work_bytes < wtp_rx_ack_work_bytes(n, window, mode), a NULL d_counts or d_work, a NULL
+   d_dgrams, d_recv_len or d_ok with n > 0, a NULL d_place or d_slot_len in cumulative mode
+   with n > 0 and window > 0, a NULL d_ack_wire with n > 0 and max_acks > 0.
+
+   d_work is the caller's scratch as for wtp_tx_build_retransmit (any alignment, contents
+   arbitrary on entry, unspecified on return, no allocation by the library; every word the
+   call reads it has written before).  wtp_rx_ack_work_bytes is monotone in n and window
+   and at most 64 KiB + 4 bytes per 1024 datagrams + 4 bytes per window slot (the window
+   term in cumulative mode only).  The header is one 16-byte store where the slot is 16-B
+   aligned (every slot of a 16-B aligned ring with ack_stride % 16 == 0), bytes otherwise.
+   Stream-ordered launches (selective: mark, emit; cumulative: init, mark, block maxima,
+   scan, emit) with no host synchronisation: d_counts[0] is never read on the host, grids
+   are sized from n and window.  The call keeps no state and reads no library table, so it
+   needs no wtp_init before a capture, and concurrent calls on different work buffers are
+   independent.  wtp_last_kernel() names "k_ack_emit". */
+#define WTP_RX_MAX_WINDOW (1u << 20)   /* cumulative mode only */
+#define WTP_RX_MAX_BATCH  (1u << 24)
+size_t wtp_rx_ack_work_bytes(size_t n, uint32_t window, uint32_t mode);
+int wtp_rx_build_acks(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len, size_t n,
+                      uint32_t mode, uint32_t seq0, uint32_t window,
+                      const uint8_t *d_ok, const uint32_t *d_place, const uint32_t *d_slot_len,
+                      void *d_ack_wire, size_t ack_stride, uint32_t skip, uint32_t max_acks,
+                      uint32_t *d_src, uint32_t *d_counts,
+                      void *d_work, size_t work_bytes, void *stream);
+
 /* ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------
    The reference's crc32(buf, size) takes any size; these give it for device-resident data
    of any size from the per-chunk CRCs, by zlib's crc32_combine identity
