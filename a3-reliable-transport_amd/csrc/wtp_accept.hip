@@ -22,19 +22,10 @@
 // would store payload bytes before the verdict, so a corrupt or duplicate datagram could
 // overwrite good data and tear a slot.  Only the owner of a slot ever writes it.
 //
-// A separate translation unit: k_fixed_braid and everything it inlines stay as they are
-// (tests/test_bench.py pins the headline kernel's machine code).
-#include <hip/hip_runtime.h>
-
+// A separate translation unit: see wtp_common.hpp.
 #include <algorithm>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
 
-#include "wtp_crc32.h"
-
-extern "C" int wtp_set_error_(int code, const char *msg);
-extern "C" void wtp_set_kernel_(const char *name);
+#include "wtp_common.hpp"
 
 #ifndef WTP_ACCEPT_NT
 #define WTP_ACCEPT_NT 1  // the place kernel's 16-B payload stores stream (nt); A/B builds: 0
@@ -46,20 +37,14 @@ extern "C" void wtp_set_kernel_(const char *name);
 namespace wtp {
 namespace dev {
 
-typedef uint32_t au32x4 __attribute__((ext_vector_type(4)));
-
 constexpr uint32_t kClaim = 0x80000000u;  // claim of datagram i = kClaim | i (n < 2^31)
 constexpr uint32_t kGroup = 16;           // lanes per datagram in k_accept_place
 constexpr uint32_t kVecs = (WTP_MAX_PAYLOAD / 16 + kGroup - 1) / kGroup;  // 91 vectors -> 6 per lane
 
-__device__ __forceinline__ uint32_t be32(const uint8_t *p) {
-    return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | uint32_t(p[3]);
-}
-
-__device__ __forceinline__ au32x4 ld16(const au32x4 *p) {
+__device__ __forceinline__ u32x4 ld16(const u32x4 *p) {
     return WTP_ACCEPT_LNT ? __builtin_nontemporal_load(p) : *p;
 }
-__device__ __forceinline__ void st16(au32x4 *p, au32x4 v) {
+__device__ __forceinline__ void st16(u32x4 *p, u32x4 v) {
     if (WTP_ACCEPT_NT)
         __builtin_nontemporal_store(v, p);
     else
@@ -135,13 +120,13 @@ k_accept_place(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t
     const uint8_t *src = ring + i * stride + WTP_HEADER_BYTES;
     uint8_t *dst = out + uint64_t(s) * WTP_MAX_PAYLOAD;
     if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0) {
-        const au32x4 *vs = reinterpret_cast<const au32x4 *>(src);
-        au32x4 *vd = reinterpret_cast<au32x4 *>(dst);
+        const u32x4 *vs = reinterpret_cast<const u32x4 *>(src);
+        u32x4 *vd = reinterpret_cast<u32x4 *>(dst);
         const uint32_t nvec = len / 16;
         if (len == WTP_MAX_PAYLOAD) {
             // a full packet, 91 vectors: rows 0 .. 4 whole, row 5 lanes 0 .. 10; all of a
             // lane's loads are in flight before its first store
-            au32x4 w[kVecs];
+            u32x4 w[kVecs];
 #pragma unroll
             for (uint32_t k = 0; k + 1 < kVecs; ++k) w[k] = ld16(vs + g + k * kGroup);
             const bool last = g + (kVecs - 1) * kGroup < WTP_MAX_PAYLOAD / 16;
@@ -169,41 +154,21 @@ k_accept_place(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t
 }  // namespace dev
 }  // namespace wtp
 
-namespace {
-
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return wtp_set_error_(code, buf);
-}
-
-int launch_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WTP_EHIP, "launch %s: %s", what, hipGetErrorString(e));
-    return WTP_OK;
-}
-
-}  // namespace
-
 extern "C" int wtp_accept_data_packets(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len, size_t n,
                                        uint32_t seq0, uint32_t window, void *d_out, uint32_t *d_slot_len,
                                        uint8_t *d_ok, uint32_t *d_place, uint32_t *d_ack, void *stream) {
     using namespace wtp;
-    if (n >= (size_t(1) << 31)) return fail(WTP_EINVAL, "n %zu >= 2^31", n);
+    int rc = check_batch(n);
+    if (rc) return rc;
     if (n > 0) {
-        if (!d_dgrams || !d_recv_len || !d_ok || !d_out || !d_slot_len) return fail(WTP_EINVAL, "null pointer");
-        if (stride < 16) return fail(WTP_EINVAL, "stride %zu < 16", stride);
+        if ((rc = check_ring(d_dgrams, stride, d_recv_len, d_ok, !d_out || !d_slot_len))) return rc;
     } else {
         if (!d_ack) return WTP_OK;  // nothing to place, nothing to report
         if (window > 0 && !d_slot_len) return fail(WTP_EINVAL, "null pointer");
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint8_t *ring = static_cast<const uint8_t *>(d_dgrams);
-    int rc = wtp_crc32_verify_batch(d_dgrams, stride, d_recv_len, n, d_ok, nullptr, stream);
+    rc = wtp_crc32_verify_batch(d_dgrams, stride, d_recv_len, n, d_ok, nullptr, stream);
     if (rc) return rc;
     {
         const uint64_t blocks = std::max<uint64_t>(1, (uint64_t(n) + 255) / 256);

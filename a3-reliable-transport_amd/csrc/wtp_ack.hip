@@ -29,24 +29,13 @@
 // Every word of d_work that a kernel reads was written by an earlier launch of the same
 // call; the call keeps no state and reads no library table.
 //
-// A separate translation unit: k_fixed_braid and everything it inlines stay as they are
-// (tests/test_bench.py pins the headline kernel's machine code).
-#include <hip/hip_runtime.h>
-
+// A separate translation unit: see wtp_common.hpp.
 #include <algorithm>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
 
-#include "wtp_crc32.h"
-
-extern "C" int wtp_set_error_(int code, const char *msg);
-extern "C" void wtp_set_kernel_(const char *name);
+#include "wtp_common.hpp"
 
 namespace wtp {
 namespace dev {
-
-typedef uint32_t ku32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t kAckBlock = 1024;  // datagrams (mark, emit) or slots (bmax, scan) per block
 constexpr uint32_t kAckWaves = kAckBlock / 64;
@@ -55,22 +44,6 @@ static_assert(kAckCounts * kAckBlock * kAckBlock == WTP_RX_MAX_BATCH, "16 counts
 static_assert(WTP_RX_MAX_WINDOW <= kAckBlock * kAckBlock, "one block maximum per lane of k_ack_scan");
 constexpr uint32_t kNever = 0xFFFFFFFFu;  // raw T: an empty slot that no datagram fills
 constexpr uint32_t kPre = 0xFFFFFFFEu;    // raw T: filled before the batch (fill time 0) unless d_place names it
-
-__device__ __forceinline__ uint32_t ack_be32(const uint8_t *p) {
-    return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | uint32_t(p[3]);
-}
-
-__device__ __forceinline__ uint32_t ack_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t ack_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = max(v, uint32_t(__shfl_xor(v, d, 64)));
-    return v;
-}
 
 // Fill time of a slot from its raw word: 0 = before the batch, j + 1 = by datagram j.
 __device__ __forceinline__ uint32_t ack_fill_time(uint32_t raw) { return raw == kPre ? 0u : raw; }
@@ -81,18 +54,10 @@ __device__ __forceinline__ bool ack_eligible(const uint8_t *__restrict__ ring, u
                                              uint32_t i, uint32_t n, uint32_t seq0, uint32_t window, uint32_t &seq) {
     if (i >= n || ok[i] == 0) return false;
     const uint32_t len = recv_len[i] - WTP_HEADER_BYTES;  // unsigned: a length below 16 is never <= 1456
-    const uint8_t *h = ring + uint64_t(i) * stride;
-    uint32_t type;
-    if ((reinterpret_cast<uintptr_t>(h) & 3u) == 0) {  // a 4-B aligned slot: two dword loads
-        const uint32_t *hw = reinterpret_cast<const uint32_t *>(h);
-        type = __builtin_bswap32(hw[0]);
-        seq = __builtin_bswap32(hw[1]);
-    } else {
-        type = ack_be32(h);
-        seq = ack_be32(h + 4);
-    }
+    const Header hd = load_header(ring + uint64_t(i) * stride);  // type, seq
+    seq = hd.seq;
     const uint32_t d = seq - seq0;  // unsigned: a wrapping window is well defined
-    return type == WTP_TYPE_DATA && len <= WTP_MAX_PAYLOAD && (d < window || d >= 0x80000000u);
+    return hd.type == WTP_TYPE_DATA && len <= WTP_MAX_PAYLOAD && (d < window || d >= 0x80000000u);
 }
 
 __global__ void __launch_bounds__(256)
@@ -127,7 +92,7 @@ __global__ void __launch_bounds__(kAckBlock)
 k_ack_bmax(const uint32_t *__restrict__ T, uint32_t window, uint32_t *__restrict__ bmax) {
     __shared__ uint32_t part[kAckWaves];
     const uint32_t t = threadIdx.x, s = blockIdx.x * kAckBlock + t;
-    const uint32_t m = ack_wave_max(s < window ? ack_fill_time(T[s]) : 0u);
+    const uint32_t m = wave_max(s < window ? ack_fill_time(T[s]) : 0u);
     if ((t & 63u) == 0) part[t / 64] = m;
     __syncthreads();
     if (t == 0) {
@@ -143,7 +108,7 @@ __global__ void __launch_bounds__(kAckBlock)
 k_ack_scan(uint32_t *T, uint32_t window, const uint32_t *__restrict__ bmax) {
     __shared__ uint32_t before[kAckWaves], wave_top[kAckWaves];
     const uint32_t t = threadIdx.x, s = blockIdx.x * kAckBlock + t, w = t / 64, lane = t & 63u;
-    const uint32_t prev = ack_wave_max(t < blockIdx.x ? bmax[t] : 0u);  // gridDim.x <= 1024
+    const uint32_t prev = wave_max(t < blockIdx.x ? bmax[t] : 0u);  // gridDim.x <= 1024
     uint32_t v = s < window ? ack_fill_time(T[s]) : 0u;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -174,8 +139,8 @@ k_ack_emit(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t *__
         c_all += c;
         c_before += b < blockIdx.x ? c : 0u;
     }
-    c_before = ack_wave_sum(c_before);
-    c_all = ack_wave_sum(c_all);
+    c_before = wave_sum(c_before);
+    c_all = wave_sum(c_all);
     uint32_t seq = 0;
     const bool ans = ack_eligible(ring, stride, recv_len, ok, i, n, seq0, window, seq);
     const uint64_t ballot = __ballot(ans);
@@ -213,12 +178,7 @@ k_ack_emit(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t *__
     // htonl{type = 3, seqNum, length = 0, checksum = crc32("") = 0}
     uint8_t *slot = wire + uint64_t(k) * ack_stride;
     if ((reinterpret_cast<uintptr_t>(slot) & 15u) == 0) {  // one 16-B store
-        ku32x4 hv;
-        hv.x = __builtin_bswap32(uint32_t(WTP_TYPE_ACK));
-        hv.y = __builtin_bswap32(seq);
-        hv.z = 0u;
-        hv.w = 0u;
-        *reinterpret_cast<ku32x4 *>(slot) = hv;
+        *reinterpret_cast<u32x4 *>(slot) = header_be(WTP_TYPE_ACK, seq, 0u, 0u);
     } else {
         // any other alignment: bytes (no access wider than the slot's alignment)
         // the loop stays rolled, or the compiler merges the sixteen stores into one
@@ -236,23 +196,7 @@ k_ack_emit(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t *__
 
 namespace {
 
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return wtp_set_error_(code, buf);
-}
-
-int launch_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WTP_EHIP, "launch %s: %s", what, hipGetErrorString(e));
-    return WTP_OK;
-}
-
-// d_work of wtp_rx_build_acks, from its first 4-B boundary on: blk[nblk], then in
+// d_work of wtp_rx_build_acks, from align4 on: blk[nblk], then in
 // cumulative mode T[window] and bmax[wblk].
 struct AckWork {
     uint32_t nblk, wblk;
@@ -267,7 +211,7 @@ AckWork ack_layout(size_t n, uint32_t window, uint32_t mode) {
     w.blk = 0;
     w.T = size_t(w.nblk) * 4;
     w.bmax = w.T + size_t(slots) * 4;
-    w.bytes = 4 + w.bmax + size_t(w.wblk) * 4;  // 4: d_work itself may be 1-B aligned
+    w.bytes = wtp::kWorkSlack + w.bmax + size_t(w.wblk) * 4;
     return w;
 }
 
@@ -284,28 +228,28 @@ extern "C" int wtp_rx_build_acks(const void *d_dgrams, size_t stride, const uint
                                  uint32_t *d_counts, void *d_work, size_t work_bytes, void *stream) {
     using namespace wtp;
     if (n > WTP_RX_MAX_BATCH) return fail(WTP_EINVAL, "n %zu > %u", n, WTP_RX_MAX_BATCH);
-    if (mode != WTP_ACK_SELECTIVE && mode != WTP_ACK_CUMULATIVE) return fail(WTP_EINVAL, "unknown mode %u", mode);
+    int rc = check_mode(mode);
+    if (rc) return rc;
     const bool cum = mode == WTP_ACK_CUMULATIVE;
     if (cum && window > WTP_RX_MAX_WINDOW) return fail(WTP_EINVAL, "window %u > %u", window, WTP_RX_MAX_WINDOW);
-    if (stride < 16) return fail(WTP_EINVAL, "stride %zu < 16", stride);
+    if ((rc = check_stride(stride))) return rc;
     if (ack_stride < 16) return fail(WTP_EINVAL, "ack_stride %zu < 16", ack_stride);
     const AckWork w = ack_layout(n, window, mode);
     if (work_bytes < w.bytes) return fail(WTP_EINVAL, "work_bytes %zu < %zu", work_bytes, w.bytes);
     if (!d_counts || !d_work) return fail(WTP_EINVAL, "null pointer");
     if (n > 0) {
-        if (!d_dgrams || !d_recv_len || !d_ok) return fail(WTP_EINVAL, "null pointer");
+        if ((rc = check_ring(d_dgrams, stride, d_recv_len, d_ok))) return rc;
         if (cum && window > 0 && (!d_place || !d_slot_len)) return fail(WTP_EINVAL, "null pointer");
         if (max_acks > 0 && !d_ack_wire) return fail(WTP_EINVAL, "null pointer");
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint8_t *ring = static_cast<const uint8_t *>(d_dgrams);
-    uint8_t *work = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_work) + 3) & ~uintptr_t(3));
+    uint8_t *work = align4(d_work);
     uint32_t *blk = reinterpret_cast<uint32_t *>(work + w.blk);
     uint32_t *bmax = reinterpret_cast<uint32_t *>(work + w.bmax);
     // T: cumulative mode with datagrams and a window; otherwise no slot is ever looked up
     uint32_t *T = cum && n > 0 && window > 0 ? reinterpret_cast<uint32_t *>(work + w.T) : nullptr;
     const uint32_t n32 = uint32_t(n);
-    int rc = WTP_OK;
     if (T) {
         hipLaunchKernelGGL(dev::k_ack_init, dim3((window + 255) / 256), dim3(256), 0, st, d_slot_len, window, T);
         if ((rc = launch_check("k_ack_init"))) return rc;

@@ -37,19 +37,11 @@
 //
 // All scratch is the caller's d_work; nothing is allocated, no state is kept, every word
 // of d_work that is read was written earlier in the same call.  A separate translation
-// unit: k_fixed_braid's machine code does not depend on it (tests/test_bench.py).
-#include <hip/hip_runtime.h>
-
+// unit: see wtp_common.hpp.
 #include <algorithm>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
 
 #include "crc32_combine.hpp"
-#include "wtp_crc32.h"
-
-extern "C" int wtp_set_error_(int code, const char *msg);
-extern "C" void wtp_set_kernel_(const char *name);
+#include "wtp_common.hpp"
 
 namespace wtp {
 namespace dev {
@@ -283,22 +275,6 @@ k_concat_var(const uint32_t *crc, const uint32_t *len, uint64_t n, uint64_t run,
 namespace {
 
 using namespace wtp;
-
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return wtp_set_error_(code, buf);
-}
-
-int launch_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WTP_EHIP, "launch %s: %s", what, hipGetErrorString(e));
-    return WTP_OK;
-}
 
 uint64_t ceil_div(uint64_t a, uint64_t b) { return a / b + (a % b != 0); }
 

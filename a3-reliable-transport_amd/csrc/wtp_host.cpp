@@ -26,10 +26,7 @@
 #include <vector>
 
 #include "crc32_combine.hpp"
-#include "wtp_crc32.h"
-
-// Defined in crc32_kernels.hip: sets the per-thread message read by wtp_last_error().
-extern "C" int wtp_set_error_(int code, const char *msg);
+#include "wtp_common.hpp"  // wtp_set_error_
 
 namespace {
 

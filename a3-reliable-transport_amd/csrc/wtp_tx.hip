@@ -48,26 +48,15 @@
 // ring shorter than the due set must hold the oldest packets; it is counted on the device
 // because the host never reads d_counts[0]: grids are sized from max_sel.
 //
-// A separate translation unit: k_fixed_braid and everything it inlines stay as they are
-// (tests/test_bench.py pins the headline kernel's machine code).
-#include <hip/hip_runtime.h>
-
+// A separate translation unit: see wtp_common.hpp.
 #include <algorithm>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
 
 #include "crc32_combine.hpp"
 #include "crc32_math.hpp"
-#include "wtp_crc32.h"
-
-extern "C" int wtp_set_error_(int code, const char *msg);
-extern "C" void wtp_set_kernel_(const char *name);
+#include "wtp_common.hpp"
 
 namespace wtp {
 namespace dev {
-
-typedef uint32_t tu32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t kTxBlock = 1024;  // slots per block of the count / select passes
 constexpr uint32_t kTxWaves = kTxBlock / 64;
@@ -105,28 +94,6 @@ struct TxTail {
 };
 __device__ const TxTail g_tx_tail{};
 
-__device__ __forceinline__ uint32_t tx_be32(const uint8_t *p) {
-    return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | uint32_t(p[3]);
-}
-
-__device__ __forceinline__ uint32_t tx_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t tx_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = max(v, uint32_t(__shfl_xor(v, d, 64)));
-    return v;
-}
-
-__device__ __forceinline__ uint32_t tx_wave_min(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = min(v, uint32_t(__shfl_xor(v, d, 64)));
-    return v;
-}
-
 // ---- ACK ingest ----------------------------------------------------------------------
 
 __global__ void __launch_bounds__(256)
@@ -140,30 +107,21 @@ k_tx_ingest(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t *_
         const uint32_t rl = recv_len[i];
         const uint8_t *h = ring + i * stride;
         bool good = rl >= WTP_HEADER_BYTES && rl <= stride && rl - WTP_HEADER_BYTES <= WTP_MAX_KERNEL_LEN;
-        uint32_t type = 0, seq = 0, sum = 0;
+        Header hd{};
         if (good) {
-            if ((reinterpret_cast<uintptr_t>(h) & 3u) == 0) {  // a 4-B aligned slot: three dword loads
-                const uint32_t *hw = reinterpret_cast<const uint32_t *>(h);
-                type = __builtin_bswap32(hw[0]);
-                seq = __builtin_bswap32(hw[1]);
-                sum = __builtin_bswap32(hw[3]);
-            } else {
-                type = tx_be32(h);
-                seq = tx_be32(h + 4);
-                sum = tx_be32(h + 12);
-            }
+            hd = load_header(h);  // type, seq, sum
             uint32_t c = 0;  // the CRC of the empty payload: a plain ACK is decided here
             if (rl > WTP_HEADER_BYTES) {
                 c = 0xFFFFFFFFu;
                 for (uint32_t b = WTP_HEADER_BYTES; b < rl; ++b) c = g_tx_table.t[0][(c ^ h[b]) & 0xFFu] ^ (c >> 8);
                 c ^= 0xFFFFFFFFu;
             }
-            good = sum == c;
+            good = hd.sum == c;
         }
         ok[i] = good ? 1 : 0;
         uint32_t where = WTP_NOT_PLACED;
-        if (good && type == WTP_TYPE_ACK) {
-            const uint32_t d = seq - seq0;  // unsigned: a wrapping window is well defined
+        if (good && hd.type == WTP_TYPE_ACK) {
+            const uint32_t d = hd.seq - seq0;  // unsigned: a wrapping window is well defined
             if (mode == WTP_ACK_SELECTIVE) {
                 if (d < inflight) {
                     where = d;
@@ -178,10 +136,10 @@ k_tx_ingest(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t *_
     }
     // one atomic per wave
     if (mode == WTP_ACK_SELECTIVE) {
-        const uint32_t sum = tx_wave_sum(fresh);
+        const uint32_t sum = wave_sum(fresh);
         if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(&counts[1], sum);
     } else {
-        const uint32_t m = tx_wave_max(amax);
+        const uint32_t m = wave_max(amax);
         if ((threadIdx.x & 63u) == 0 && m) atomicMax(&counts[1], m);
     }
 }
@@ -199,7 +157,7 @@ k_tx_lead(uint32_t inflight, const uint32_t *__restrict__ acked, uint32_t *count
             break;
         }
     }
-    mine = tx_wave_min(mine);
+    mine = wave_min(mine);
     if ((threadIdx.x & 63u) == 0 && mine < __hip_atomic_load(&counts[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
         atomicMin(&counts[0], mine);
 }
@@ -221,7 +179,7 @@ k_tx_window(uint32_t mode, uint32_t inflight, uint32_t *acked, uint32_t *counts)
                 acked[s] = 1;
                 ++fresh;
             }
-        fresh = tx_wave_sum(fresh);
+        fresh = wave_sum(fresh);
         if ((t & 63u) == 0) part[t / 64] = fresh;
         __syncthreads();  // every lane has read counts[1] and stored its slots
         if (t == 0) {
@@ -286,7 +244,7 @@ k_tx_select(const uint32_t *__restrict__ acked, uint32_t *sent, uint32_t infligh
     __shared__ uint32_t before[kTxWaves], all[kTxWaves], wave_due[kTxWaves];
     const uint32_t t = threadIdx.x, s = blockIdx.x * kTxBlock + t, w = t / 64, lane = t & 63u;
     const uint32_t c = t < nblk ? blk[t] : 0;
-    const uint32_t sum_before = tx_wave_sum(t < blockIdx.x ? c : 0), sum_all = tx_wave_sum(c);
+    const uint32_t sum_before = wave_sum(t < blockIdx.x ? c : 0), sum_all = wave_sum(c);
     const bool due = tx_due(acked, sent, s, inflight, now, timeout, flags);
     const uint64_t ballot = __ballot(due);
     if (lane == 0) {
@@ -340,10 +298,10 @@ k_tx_emit(const uint8_t *__restrict__ pay, uint64_t total_bytes, uint32_t seq0, 
     const uint32_t seg0 = g * kTxSeg, seg = len > seg0 ? min(len - seg0, kTxSeg) : 0;
     uint32_t c = 0xFFFFFFFFu;
     if (vec && len == WTP_MAX_PAYLOAD) {
-        const tu32x4 *vs = reinterpret_cast<const tu32x4 *>(src + seg0);
-        tu32x4 *vd = reinterpret_cast<tu32x4 *>(dst + seg0);
+        const u32x4 *vs = reinterpret_cast<const u32x4 *>(src + seg0);
+        u32x4 *vd = reinterpret_cast<u32x4 *>(dst + seg0);
         const uint32_t nv = seg / 16;  // 6, lane 15: 1
-        tu32x4 v[kTxVecs];
+        u32x4 v[kTxVecs];
         v[0] = vs[0];
 #pragma unroll
         for (uint32_t r = 1; r < kTxVecs; ++r)
@@ -378,14 +336,8 @@ k_tx_emit(const uint8_t *__restrict__ pay, uint64_t total_bytes, uint32_t seq0, 
     for (int d = kTxGroup / 2; d > 0; d >>= 1) crc ^= __shfl_xor(crc, d, kTxGroup);
     const uint32_t hdr[4] = {WTP_TYPE_DATA, seq0 + s, len, crc};
     if (vec) {
-        if (g == 0) {  // the header: one 16-B store, big-endian fields
-            tu32x4 hv;
-            hv.x = __builtin_bswap32(hdr[0]);
-            hv.y = __builtin_bswap32(hdr[1]);
-            hv.z = __builtin_bswap32(hdr[2]);
-            hv.w = __builtin_bswap32(hdr[3]);
-            *reinterpret_cast<tu32x4 *>(slot) = hv;
-        }
+        // the header: one 16-B store
+        if (g == 0) *reinterpret_cast<u32x4 *>(slot) = header_be(hdr[0], hdr[1], hdr[2], hdr[3]);
     } else {
         const uint32_t word = g < 4 ? hdr[0] : g < 8 ? hdr[1] : g < 12 ? hdr[2] : hdr[3];
         slot[g] = uint8_t(word >> (8 * (3 - g % 4)));  // big-endian fields, one byte per lane
@@ -398,24 +350,8 @@ k_tx_emit(const uint8_t *__restrict__ pay, uint64_t total_bytes, uint32_t seq0, 
 
 namespace {
 
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return wtp_set_error_(code, buf);
-}
-
-int launch_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WTP_EHIP, "launch %s: %s", what, hipGetErrorString(e));
-    return WTP_OK;
-}
-
-// d_work of wtp_tx_build_retransmit, from its first 4-B boundary on: picked[m],
-// blk[blocks]; m = min(max_sel, inflight) entries (no more can be due).
+// d_work of wtp_tx_build_retransmit, from align4 on: picked[m], blk[blocks];
+// m = min(max_sel, inflight) entries (no more can be due).
 struct TxWork {
     uint32_t m, blocks;
     size_t picked, blk, bytes;
@@ -427,7 +363,7 @@ TxWork tx_layout(uint32_t inflight, uint32_t max_sel) {
     w.blocks = (inflight + wtp::dev::kTxBlock - 1) / wtp::dev::kTxBlock;
     w.picked = 0;
     w.blk = size_t(w.m) * 4;
-    w.bytes = 4 + w.blk + size_t(w.blocks) * 4;  // 4: d_work itself may be 1-B aligned
+    w.bytes = wtp::kWorkSlack + w.blk + size_t(w.blocks) * 4;
     return w;
 }
 
@@ -437,18 +373,15 @@ extern "C" int wtp_tx_ingest_acks(const void *d_dgrams, size_t stride, const uin
                                   uint32_t mode, uint32_t seq0, uint32_t inflight, uint32_t *d_acked, uint8_t *d_ok,
                                   uint32_t *d_hit, uint32_t *d_counts, void *stream) {
     using namespace wtp;
-    if (n >= (size_t(1) << 31)) return fail(WTP_EINVAL, "n %zu >= 2^31", n);
+    int rc = check_batch(n);
+    if (rc) return rc;
     if (inflight > WTP_TX_MAX_INFLIGHT) return fail(WTP_EINVAL, "inflight %u > %u", inflight, WTP_TX_MAX_INFLIGHT);
-    if (mode != WTP_ACK_SELECTIVE && mode != WTP_ACK_CUMULATIVE) return fail(WTP_EINVAL, "unknown mode %u", mode);
+    if ((rc = check_mode(mode))) return rc;
     if (!d_counts || (inflight > 0 && !d_acked)) return fail(WTP_EINVAL, "null pointer");
-    if (n > 0) {
-        if (!d_dgrams || !d_recv_len || !d_ok) return fail(WTP_EINVAL, "null pointer");
-        if (stride < 16) return fail(WTP_EINVAL, "stride %zu < 16", stride);
-    }
+    if (n > 0 && (rc = check_ring(d_dgrams, stride, d_recv_len, d_ok))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(d_counts, 0, 2 * sizeof(uint32_t), st);
     if (e != hipSuccess) return fail(WTP_EHIP, "hipMemsetAsync(d_counts): %s", hipGetErrorString(e));
-    int rc = WTP_OK;
     if (n > 0 || mode == WTP_ACK_SELECTIVE) {  // n == 0: one block, which only sets d_counts[0]
         const uint64_t blocks = std::max<uint64_t>(1, (uint64_t(n) + 255) / 256);
         hipLaunchKernelGGL(dev::k_tx_ingest, dim3(unsigned(blocks)), dim3(256), 0, st,
@@ -487,7 +420,7 @@ extern "C" int wtp_tx_build_retransmit(const void *d_payloads, size_t total_byte
     if (inflight > 0 && (!d_payloads || !d_acked || !d_sent_ms)) return fail(WTP_EINVAL, "null pointer");
     if (w.m > 0 && !d_wire) return fail(WTP_EINVAL, "null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    uint8_t *work = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_work) + 3) & ~uintptr_t(3));
+    uint8_t *work = align4(d_work);
     uint32_t *picked = reinterpret_cast<uint32_t *>(work + w.picked);
     uint32_t *blk = reinterpret_cast<uint32_t *>(work + w.blk);
     int rc = WTP_OK;

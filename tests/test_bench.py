@@ -224,6 +224,25 @@ def test_traffic_null_unless_kernel_code_matches(tmp_path):
     assert v is None
 
 
+def test_codeobj_all_lists_every_translation_units_kernels():
+    """`tools/codeobj.py --all LIB` (two builds' outputs diff to the kernels a change touched):
+    its entry for the headline kernel is kernel_code_sha256's, and it reaches the kernels of
+    the protocol translation units, which sit in offload bundles of their own."""
+    import subprocess
+    sys.path.insert(0, os.path.join(ROOT, "a3-reliable-transport_amd"))
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import codeobj
+    import wtp_crc32 as W
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "codeobj.py"), "--all", W.LIB_PATH],
+                         check=True, capture_output=True, text=True).stdout
+    table = json.loads(out)
+    want = codeobj.kernel_code_sha256(W.LIB_PATH, codeobj.HEADLINE_KERNEL)
+    assert table[want["kernel"]] == {"code_bytes": want["code_bytes"], "sha256": want["sha256"]}
+    for name in ("k_accept_place", "k_concat_fold", "k_tx_select", "k_ack_emit"):
+        hits = [k for k in table if name in k]
+        assert len(hits) == 1 and table[hits[0]]["code_bytes"] > 0 and len(table[hits[0]]["sha256"]) == 64, name
+
+
 def test_extra_leg_failure_is_reported_not_fatal(monkeypatch):
     """A leg that cannot run (here the C4 leg's RCCL init raises) is recorded in the line
     and the other leg still runs; a leg with a wrong result vector fails the parity."""

@@ -277,6 +277,42 @@ def test_arbitrary_place(W, mode, window, n):
     assert e > n // 8
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_more_than_one_block_count_per_lane(W, mode):
+    """2^20 + 1025 header-only DATA datagrams (stride 16, length 0, checksum 0) are 1026
+    blocks of k_ack_mark, so a lane of k_ack_emit sums two block counts: the smallest batch
+    that does.  d_ok (about half ones), d_place and d_slot_len are supplied directly: 2049
+    datagrams spread over the batch name the window's slots in rising order, shuffled within
+    runs of 16, so the running ACK climbs through the whole batch."""
+    n, window, seq0 = (1 << 20) + 1025, 2049, 0xFFFFFF00
+    rng = np.random.default_rng(n + mode)
+    hdr = np.zeros((n, 4), dtype=">u4")
+    hdr[:, 0] = 2
+    hdr[:, 1] = (seq0 + rng.integers(-50, window + 50, n)) & A.M32  # some below and some past the window
+    ring, rl = hdr.view(np.uint8).reshape(-1), np.full(n, 16, np.uint32)
+    ok = (rng.random(n) < 0.5).astype(np.uint8)
+    place = np.where(rng.random(n) < 0.001, window + 3, A.NOT_PLACED).astype(np.uint32)  # >= window: not placed
+    place[np.sort(rng.choice(n, window, replace=False))] = np.concatenate(
+        [c[rng.permutation(c.size)] for c in np.array_split(np.arange(window), window // 16)])
+    sl = A.prefilled(rng, window)
+    seq, idx, (emitted, total) = A.build_acks(ring, 16, rl, mode, seq0, window, place, sl, ok=ok, vectorised=True)
+    assert n // 3 < emitted == total < n // 2
+    if mode == A.CUMULATIVE:  # the running ACK still moves past datagram 2^20
+        assert np.unique(seq).size > 100 and idx[np.flatnonzero(np.diff(seq.astype(np.int64)))[-1] + 1] > 1 << 20
+
+    d, r, okt = torch.from_numpy(ring).cuda(), Words(rl), torch.from_numpy(ok).cuda()
+    pl, slw, src, counts = Words(place), Words(sl), Words(SENT, n + 2), Words(0x77777777, 2)
+    wire = torch.full((n + 2, 16), 0xA5, dtype=torch.uint8, device="cuda")
+    W.rx_build_acks(d, 16, r.t, n, mode, seq0, window, okt, pl.t, slw.t, wire, 16, 0, n, src.t, counts.t)
+    torch.cuda.synchronize()
+    assert tuple(counts.get()) == (emitted, total)
+    assert np.array_equal(src.get(), np.concatenate([idx, np.full(n + 2 - emitted, SENT, np.uint32)]))
+    rows = wire.cpu().numpy()
+    assert np.array_equal(rows[:emitted], A.ack_bytes(seq)) and (rows[emitted:] == 0xA5).all()
+    assert np.array_equal(pl.get(), place) and np.array_equal(slw.get(), sl) and np.array_equal(r.get(), rl)
+    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+
+
 def test_graph_replay(W):
     """accept + build_acks captured into one graph and replayed three times into cleared
     outputs and a scribbled work buffer; then two graphs on two streams with their own work

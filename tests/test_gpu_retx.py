@@ -236,25 +236,31 @@ def _state(inflight, due_mask):
     return acked, ((NOW - age) & M.M32).astype(np.uint32)
 
 
+BLOCK_EDGES = (1023, 1024, 1025, 2049)  # around the 1024-slot blocks of k_tx_count / k_tx_select
+
+
 def _fractions(inflight):
     s = np.arange(inflight)
+    if inflight in BLOCK_EDGES:  # a sparse and a dense due set
+        return {"hundredth": np.random.default_rng(inflight).random(inflight) < 0.01, "all": s >= 0}
     return {"none": s < 0, "one": s == inflight * 2 // 3, "alternate": s % 2 == 0,
             "tenth": np.random.default_rng(inflight).random(inflight) < 0.1, "all": s >= 0}
 
 
-LAST_LEN = {1: 1, 64: 15, 65: 16, 256: 17, 257: 1455, 1000: 1, 70000: 15}
+LAST_LEN = {1: 1, 64: 15, 65: 16, 256: 17, 257: 1455, 1000: 1, 1023: 1456, 1024: 1, 1025: 16, 2049: 15, 70000: 15}
 
 
 @pytest.mark.parametrize("inflight", sorted(LAST_LEN))
 def test_select_and_emit(W, inflight):
-    """Due fractions x ring sizes; 70 000 slots cross 69 scan blocks (its bytes are compared
-    with the builder's wire image on the device only)."""
+    """Due fractions x ring sizes; 70 000 slots cross 69 scan blocks, and the windows of
+    BLOCK_EDGES end one slot before, at and one slot after a block's end (above 1000 slots
+    the bytes are compared with the builder's wire image on the device only)."""
     seq0 = 0xFFFFFFF0 if inflight % 2 else 7
     src = Source(W, inflight, LAST_LEN[inflight], seq0, host=inflight <= 1000)
     for name, mask in _fractions(inflight).items():
         acked, sent = _state(inflight, mask)
         due = int(mask.sum())
-        full = inflight <= 1000 or name == "tenth"  # the 100 MB window: every ring size at one fraction only
+        full = inflight <= 2049 or name == "tenth"  # the 100 MB window: every ring size at one fraction only
         for max_sel in sorted({0, 1, max(due - 1, 0), due, due + 7} if full else {due + 7}):
             sel, sent2, (emitted, got_due) = retx(W, src, acked, sent, NOW, TIMEOUT, 0, max_sel)
             assert got_due == due and emitted == min(due, max_sel), (name, max_sel)

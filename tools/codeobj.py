@@ -1,11 +1,14 @@
 """Read the gfx950 code object out of a HIP shared library, in pure Python (no ROCm tools
 needed, so bench.py can use it on the GPU box): the .hip_fatbin section of the host ELF
-holds a Clang offload bundle whose gfx950 entry is an AMDGPU ELF; its symbol table gives
-each kernel's machine code.
+holds one Clang offload bundle per translation unit, whose gfx950 entry is an AMDGPU ELF;
+its symbol table gives each kernel's machine code.
 
 kernel_code_sha256(lib, pattern) hashes the code bytes of the kernel whose mangled name
 matches `pattern`.  bench.py stamps roofline.traffic with it: the committed PMC pass
 (profiles/pmc_traffic.json) counts for the kernel it measured and for no other.
+
+`codeobj.py --all LIB` prints {mangled name: {"code_bytes", "sha256"}} for every kernel of
+every translation unit: diff two builds' outputs to see which kernels a change touched.
 """
 from __future__ import annotations
 
@@ -32,27 +35,36 @@ def _sections(elf: bytes) -> dict:
     return out
 
 
-def gfx950_code_object(lib_path: str) -> bytes:
+def gfx950_code_objects(lib_path: str) -> list:
+    """The gfx950 entry of every offload bundle, one bundle per translation unit, in link order."""
     blob = open(lib_path, "rb").read()
     secs = _sections(blob)
     if ".hip_fatbin" not in secs:
         raise ValueError(f"{lib_path}: no .hip_fatbin section")
     off, size = secs[".hip_fatbin"][:2]
     fb = blob[off:off + size]
+    out = []
     at = fb.find(_BUNDLE_MAGIC)
-    if at < 0:
-        raise ValueError(f"{lib_path}: no uncompressed offload bundle")
-    p = at + len(_BUNDLE_MAGIC)
-    n, = struct.unpack_from("<Q", fb, p)
-    p += 8
-    for _ in range(n):
-        eoff, esize, tlen = struct.unpack_from("<QQQ", fb, p)
-        p += 24
-        triple = fb[p:p + tlen].decode()
-        p += tlen
-        if triple.endswith("gfx950"):
-            return fb[at + eoff:at + eoff + esize]
-    raise ValueError(f"{lib_path}: no gfx950 entry in the offload bundle")
+    while at >= 0:
+        p = at + len(_BUNDLE_MAGIC)
+        n, = struct.unpack_from("<Q", fb, p)
+        p += 8
+        for _ in range(n):
+            eoff, esize, tlen = struct.unpack_from("<QQQ", fb, p)
+            p += 24
+            triple = fb[p:p + tlen].decode()
+            p += tlen
+            if triple.endswith("gfx950"):
+                out.append(fb[at + eoff:at + eoff + esize])
+        at = fb.find(_BUNDLE_MAGIC, p)
+    if not out:
+        raise ValueError(f"{lib_path}: no uncompressed offload bundle with a gfx950 entry")
+    return out
+
+
+def gfx950_code_object(lib_path: str) -> bytes:
+    """The first translation unit's (crc32_kernels.hip: the headline kernel's)."""
+    return gfx950_code_objects(lib_path)[0]
 
 
 def kernel_symbols(co: bytes) -> dict:
@@ -96,7 +108,19 @@ def kernel_code_sha256(lib_path: str, pattern: str) -> dict:
 # launcher's long-batch epilogue, which 1 M packets use)
 HEADLINE_KERNEL = r"k_fixed_braidILi6ELi0ENS0_11CrcHoldBEpiE"
 
+
+def all_kernels(lib_path: str) -> dict:
+    """{mangled name: {"code_bytes", "sha256"}} of every kernel: two builds' outputs diff to
+    the kernels whose machine code a change touched."""
+    return {n: {"code_bytes": size, "sha256": hashlib.sha256(co[off:off + size]).hexdigest()}
+            for co in gfx950_code_objects(lib_path) for n, (off, size) in sorted(kernel_symbols(co).items())}
+
+
 if __name__ == "__main__":
     import json
     import sys
-    print(json.dumps(kernel_code_sha256(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else HEADLINE_KERNEL)))
+    args = [a for a in sys.argv[1:] if a != "--all"]
+    if len(args) < len(sys.argv) - 1:
+        print(json.dumps(all_kernels(args[0]), indent=1))
+    else:
+        print(json.dumps(kernel_code_sha256(args[0], args[1] if len(args) > 1 else HEADLINE_KERNEL)))
