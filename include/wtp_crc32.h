@@ -142,7 +142,9 @@ int wtp_crc32_batch_packed(const void *d_base, size_t base_bytes, const uint64_t
    ntohl(header.checksum) == crc32(payload), else 0 (drop, no ACK).  A recv_len
    above stride (more than the ring slot holds; recvfrom cannot return it) is
    malformed: ok 0.  d_crc_out may be NULL; otherwise it receives the computed CRCs
-   (0 for runts and malformed lengths).  Fast path: a 16-B aligned ring with
+   (0 for runts and malformed lengths).  A payload above WTP_MAX_KERNEL_LEN bytes
+   (recv_len - 16 > 4096, in a slot that holds it) is not hashed: ok 0, crc 0, and status
+   bit 0 (wtp_device_status) is set.  Fast path: a 16-B aligned ring with
    stride % 16 == 0 (e.g. 1472 = header + 1456, or wReceiver's 1504-B slots holding the
    reference's 1500-B receive buffer) runs the braided kernel over the first
    min(stride - 16, 1456) payload bytes of every slot and decides the datagrams of

@@ -1,8 +1,10 @@
 """Sequential model of the device-side sender window (include/wtp_crc32.h:
 wtp_tx_ingest_acks, wtp_tx_build_retransmit), written from the header's semantics: one
 datagram, then one slot, at a time over a window the caller owns.  ok comes from
-oracle.verify_datagrams, pinned to the reference.  Entry state is never modified: copies
-are returned."""
+oracle.verify_datagrams, pinned to the reference, cut at the kernels' payload limit
+(verify_limited).  Entry state is never modified: copies are returned.  A vectorised numpy
+path gives the same results for windows of 2^20 slots (tests/test_retx_model.py checks it
+against the literal loops)."""
 import numpy as np
 
 import oracle as O
@@ -20,13 +22,40 @@ def ack_datagram(seq, ptype=3, checksum=0, payload=b""):
     return h + bytes(payload)
 
 
-def ingest(ring, stride, recv_len, mode, seq0, inflight, acked):
+MAX_KERNEL_LEN = 4096  # WTP_MAX_KERNEL_LEN
+
+
+def verify_limited(ring, stride, recv_len):
+    """(ok, crc) as wtp_crc32_verify_batch writes them: the oracle's verdict (the reference
+    has no length limit), except that a payload above WTP_MAX_KERNEL_LEN is not ok and gets
+    crc 0.  The one place where the models take the limit from."""
+    ring = np.ascontiguousarray(ring, dtype=np.uint8)
+    recv_len = np.ascontiguousarray(recv_len, dtype=np.uint32)
+    if recv_len.size == 0:
+        return np.zeros(0, np.uint8), np.zeros(0, np.uint32)
+    ok, crc = O.verify_datagrams(ring, stride, recv_len)
+    within = recv_len.astype(np.int64) - 16 <= MAX_KERNEL_LEN
+    return (ok * within).astype(np.uint8), (crc * within).astype(np.uint32)
+
+
+def headers(ring, stride, n):
+    """(type, seqNum) of n datagrams as uint32 arrays (whatever bytes are there)."""
+    if n == 0:
+        return np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+    idx = (np.arange(n, dtype=np.int64) * stride)[:, None] + np.arange(8)
+    h = np.ascontiguousarray(ring[idx]).view(">u4")
+    return h[:, 0].astype(np.uint32), h[:, 1].astype(np.uint32)
+
+
+def ingest(ring, stride, recv_len, mode, seq0, inflight, acked, vectorised=False):
     """Returns (ok, hit, acked, (advance, newly))."""
     ring = np.ascontiguousarray(ring, dtype=np.uint8)
     recv_len = np.ascontiguousarray(recv_len, dtype=np.uint32)
     n = recv_len.size
     acked = np.array(acked, dtype=np.uint32, copy=True)
-    ok = O.verify_datagrams(ring, stride, recv_len)[0] if n else np.zeros(0, np.uint8)
+    ok = verify_limited(ring, stride, recv_len)[0]
+    if vectorised:
+        return (ok,) + _ingest_vectorised(ring, stride, n, ok, mode, seq0, inflight, acked)
     hit = np.full(n, NOT_PLACED, dtype=np.uint32)
     newly = 0
     for i in range(n):
@@ -53,15 +82,42 @@ def ingest(ring, stride, recv_len, mode, seq0, inflight, acked):
     return ok, hit, acked, (lead, newly)
 
 
+def _ingest_vectorised(ring, stride, n, ok, mode, seq0, inflight, acked):
+    """The loop above without a loop: the batch's marks are a set (selective) or a prefix
+    (cumulative), so their order only matters for d_hit, which is per datagram."""
+    types, seqs = headers(ring, stride, n)
+    d = (seqs.astype(np.int64) - seq0) & M32
+    counts = (ok != 0) & (types == 3) & ((d < inflight) if mode == SELECTIVE else ((d > 0) & (d <= inflight)))
+    hit = np.where(counts, d, NOT_PLACED).astype(np.uint32)
+    if mode == SELECTIVE:
+        marks = np.unique(d[counts])
+    else:
+        marks = np.arange(int(d[counts].max()) if counts.any() else 0)
+    newly = int((acked[marks] == 0).sum())
+    acked[marks] = np.maximum(acked[marks], 1)
+    zeros = np.flatnonzero(acked[:inflight] == 0)
+    return hit, acked, (int(zeros[0]) if zeros.size else inflight, newly)
+
+
 def slot_len(s, total_bytes):
     return min(MAXP, total_bytes - s * MAXP)
 
 
-def retransmit(payloads, total_bytes, seq0, inflight, acked, sent_ms, now_ms, timeout_ms, flags, max_sel, build=True):
+def retransmit(payloads, total_bytes, seq0, inflight, acked, sent_ms, now_ms, timeout_ms, flags, max_sel, build=True,
+               vectorised=False):
     """Returns (sel, dgrams, sent_ms, (emitted, due)): sel the emitted slots in order, dgrams
     their datagrams as bytes (left empty with build=False, for windows whose bytes the
     caller compares by other means)."""
     sent_ms = np.array(sent_ms, dtype=np.uint32, copy=True)
+    if vectorised:
+        age = (now_ms - sent_ms[:inflight].astype(np.int64)) & M32
+        is_due = (np.asarray(acked)[:inflight] == 0) & (bool(flags & RETX_ALL) | (age > timeout_ms))
+        sel = np.flatnonzero(is_due)
+        due, sel = sel.size, sel[:max_sel]
+        sent_ms[sel] = now_ms & M32
+        dgrams = [O.build_datagram((seq0 + int(s)) & M32, bytes(payloads[int(s) * MAXP:int(s) * MAXP + slot_len(int(s), total_bytes)]))
+                  for s in sel] if build else []  # over the emitted datagrams, not the window
+        return sel.astype(np.uint32), dgrams, sent_ms, (int(sel.size), int(due))
     sel, dgrams, due = [], [], 0
     for s in range(inflight):
         if acked[s] != 0:
@@ -76,6 +132,32 @@ def retransmit(payloads, total_bytes, seq0, inflight, acked, sent_ms, now_ms, ti
                 dgrams.append(O.build_datagram((seq0 + s) & M32, bytes(payloads[s * MAXP:s * MAXP + ln])))
             sent_ms[s] = now_ms & M32
     return np.array(sel, dtype=np.uint32), dgrams, sent_ms, (len(sel), due)
+
+
+# ---- datagrams around the kernels' payload limit ---------------------------------------------
+def limit_corpus(stride, ptype, count, seed, window, over=True):
+    """`count` datagrams of type `ptype` with valid checksums whose payload lengths cycle
+    through 0, 1, 3, 4, 255, 1456, 1457, 4095, 4096, 4097 and stride - 16 (`over` False: only
+    those of at most WTP_MAX_KERNEL_LEN bytes, in the same order), in seeded random order,
+    plus one datagram with a flipped payload bit for each length above 1456.  seqNums are
+    below `window`: payloads of at most 1456 bytes in its lower half, each seqNum once,
+    longer ones in its upper half.  Returns (dgrams, payload lengths)."""
+    rng = np.random.default_rng(seed)
+    lens = [0, 1, 3, 4, 255, MAXP, MAXP + 1, 4095, 4096, 4097, stride - 16]
+    pick = [lens[i % len(lens)] for i in range(count)] + [-ln for ln in lens if ln > MAXP]
+    pick = [pick[i] for i in rng.permutation(len(pick))]
+    low = iter(rng.permutation(window // 2).tolist())
+    dgrams, out = [], []
+    for k, ln in enumerate(pick):
+        corrupt, ln = ln < 0, abs(ln)
+        seq = next(low) if ln <= MAXP else window // 2 + int(rng.integers(0, window - window // 2))
+        d = bytearray(O.build_datagram(seq, O.synth_fill_np(ln, start_byte=97 * k, seed=seed).tobytes(), ptype))
+        if corrupt:
+            d[16 + int(rng.integers(0, ln))] ^= 0x04
+        if over or ln <= MAX_KERNEL_LEN:
+            dgrams.append(bytes(d))
+            out.append(ln)
+    return dgrams, np.array(out, dtype=np.int64)
 
 
 # ---- a whole transfer between two windows ------------------------------------------------

@@ -1350,6 +1350,64 @@ def test_verify_misaligned_ring_takes_general_path(W):
     assert np.array_equal(ok, want_ok) and np.array_equal(crc, want_crc)
 
 
+@pytest.mark.parametrize("off", [0, 4])
+@pytest.mark.parametrize("stride", [4128, 5000, 16384])
+def test_verify_payload_limit(W, stride, off):
+    """Payloads of 0 .. 4097 and stride - 16 bytes with valid checksums, and a corrupt one of
+    each length above 1456 (retx_model.limit_corpus), in rings whose slots hold them: up to
+    WTP_MAX_KERNEL_LEN bytes the verdict and the CRC are the oracle's, above it ok 0, crc 0
+    and status bit 0 (retx_model.verify_limited; the oracle, like the reference, has no
+    limit).  A 16-B aligned ring at stride 4128 or 16 384 takes the braided launch, which
+    decides only the 1472-byte datagrams and leaves the others to its fix-up phase; stride
+    5000 and a base at offset 4 take the general kernel."""
+    import retx_model as M
+    W.device_status(0, clear=True)
+    for over in (True, False):
+        dg, lens = M.limit_corpus(stride, 2, 330, stride + off, 512, over=over)
+        buf, rl = M.make_ring(dg, stride)
+        n = rl.size
+        want_ok, want_crc = M.verify_limited(buf, stride, rl)
+        o_ok, o_crc = O.verify_datagrams(buf, stride, rl)
+        long = lens > M.MAX_KERNEL_LEN
+        assert long.any() == over and o_ok[long].sum() == (60 if over else 0) and not want_ok[long].any()
+        assert np.array_equal(want_ok[~long], o_ok[~long]) and np.array_equal(want_crc[~long], o_crc[~long])
+        assert want_ok.sum() == 9 * 30 and (want_ok[lens == 4096] == 1).sum() == 30 and (rl <= stride).all()
+        ok, crc = _verify_dev(W, buf, stride, rl, n, True, offset=off)
+        assert np.array_equal(ok, want_ok), (lens[ok != want_ok][:10], np.flatnonzero(ok != want_ok)[:10])
+        assert np.array_equal(crc, want_crc), (lens[crc != want_crc][:10], np.flatnonzero(crc != want_crc)[:10])
+        assert (W.device_status(0, clear=True) & 1) == int(over)
+
+
+def test_accept_payload_limit(W):
+    """The same corpus through wtp_accept_data_packets at stride 4128: d_ok is verify's,
+    nothing above 1456 bytes is placed and the window's upper half, which only those
+    datagrams name, stays as it was."""
+    import accept_model
+    import retx_model as M
+    W.device_status(0, clear=True)
+    stride, window, seq0 = 4128, 512, 0
+    dg, lens = M.limit_corpus(stride, 2, 330, 77, window)
+    buf, rl = M.make_ring(dg, stride)
+    n = rl.size
+    img0, sl0 = np.full(window * 1456, 0xA5, np.uint8), np.full(window, 0xFFFFFFFF, np.uint32)
+    _, want_place, want_img, want_sl, want_ack = accept_model.accept(buf, stride, rl, seq0, window, img0, sl0)
+    want_ok = M.verify_limited(buf, stride, rl)[0]
+    d, r = dev_u8(buf), torch.from_numpy(rl.view(np.int32)).cuda()
+    img, sl = dev_u8(img0), torch.from_numpy(sl0.view(np.int32)).cuda()
+    ok = torch.full((n,), 7, dtype=torch.uint8, device="cuda")
+    place, ack = u32_out(n), u32_out(1)
+    W.accept_data_packets(d, stride, r, n, seq0, window, img, sl, ok, place, ack)
+    ok2, _ = _verify_dev(W, buf, stride, rl, n, False)
+    got_place = to_u32(place, n)
+    assert np.array_equal(ok.cpu().numpy(), want_ok) and np.array_equal(ok2, want_ok)
+    assert np.array_equal(got_place, want_place) and int(to_u32(ack, 1)[0]) == want_ack
+    assert np.array_equal(img.cpu().numpy(), want_img) and np.array_equal(sl.cpu().numpy().view(np.uint32), want_sl)
+    assert (got_place[lens > 1456] == 0xFFFFFFFF).all() and (got_place[(lens <= 1456)] != 0xFFFFFFFF).all()
+    assert (want_img[window // 2 * 1456:] == 0xA5).all() and (want_sl[window // 2:] == 0xFFFFFFFF).all()
+    assert np.array_equal(d.cpu().numpy(), buf) and np.array_equal(r.cpu().numpy().view(np.uint32), rl)
+    assert W.device_status(0, clear=True) & 1  # accept's verify flags the payloads above the limit
+
+
 def test_verify_large_ring_properties(W, golden_dir):
     """1M full 1472-B datagrams built on the device: every one verifies; one flipped
     payload bit per 4099 datagrams is caught exactly there; the whole CRC vector vs the

@@ -54,6 +54,16 @@ def literal_timeout(window, now, timeout, resend_all, max_sel):
     return out, due
 
 
+def _ack_batch(rng, seq0, inflight, nmax=30):
+    """One seeded ACK batch in a stride-16 ring: seqNums from three below the window to three
+    past it.  kind 0: bad checksum, 1: DATA type, else a valid ACK."""
+    n = int(rng.integers(0, nmax))
+    seqs = (seq0 + rng.integers(-3, inflight + 4, n)) & M.M32
+    kind = rng.integers(0, 8, n)
+    dg = [M.ack_datagram(int(s), ptype=2 if k == 1 else 3, checksum=int(k == 0)) for s, k in zip(seqs, kind)]
+    return (seqs, kind) + M.make_ring(dg, 16)
+
+
 @pytest.mark.parametrize("mode", [M.SELECTIVE, M.CUMULATIVE])
 def test_model_equals_literal_loop(mode):
     rng = np.random.default_rng(0x7E57 + mode)
@@ -67,11 +77,7 @@ def test_model_equals_literal_loop(mode):
         src = O.synth_fill_np(total, start_byte=trace)
         window = deque({"seq": (seq0 + s) & M.M32, "acked": bool(acked[s]), "sent": int(sent[s])} for s in range(inflight))
         for batch in range(3):
-            n = int(rng.integers(0, 30))
-            seqs = (seq0 + rng.integers(-3, inflight + 4, n)) & M.M32
-            kind = rng.integers(0, 8, n)  # 0: bad checksum, 1: DATA type, else a valid ACK
-            dg = [M.ack_datagram(int(s), ptype=2 if k == 1 else 3, checksum=int(k == 0)) for s, k in zip(seqs, kind)]
-            ring, rl = M.make_ring(dg, 16)
+            seqs, kind, ring, rl = _ack_batch(rng, seq0, inflight)
             ok, hit, acked2, (adv, newly) = M.ingest(ring, 16, rl, mode, seq0, inflight, acked)
             want = literal_acks(window, [(k > 1, int(s)) for s, k in zip(seqs, kind)], mode)
             assert (adv, newly) == want
@@ -90,6 +96,95 @@ def test_model_equals_literal_loop(mode):
             for s, d in zip(sel, dgrams):
                 assert d == O.build_datagram((seq0 + int(s)) & M.M32, src[int(s) * M.MAXP:(int(s) + 1) * M.MAXP].tobytes())
             sent = sent2
+
+
+BIG_WINDOWS = (1023, 1024, 1025, 2048, 2049, 2050, 3000)  # around k_tx_window's 1024-lane fill and two of its steps
+
+
+@pytest.mark.parametrize("mode", [M.SELECTIVE, M.CUMULATIVE])
+def test_vectorised_model_equals_literal_model(mode):
+    """The numpy paths of the model (what the GPU tests of 2^20-slot windows compare with)
+    against its literal loops (pinned to the deque above), on 320 traces of three carried
+    batches each from the same generator; every 16th trace has a window of BIG_WINDOWS with
+    a pre-ACKed leading run.  The classes of datagrams and the window edges the traces
+    reach are counted, so a change of the generator cannot empty one unnoticed."""
+    rng = np.random.default_rng(0xBEC7 + mode)
+    seen = dict(dup=0, outside=0, edge=0, bad=0, wrong_type=0, lead_past_1024=0, lead_past_2049=0, top_past_1024=0,
+                ring_short=0)
+    for trace in range(320):
+        big = trace % 16 == 0
+        inflight = BIG_WINDOWS[(trace // 16) % len(BIG_WINDOWS)] if big else int(rng.integers(0, 40))
+        seq0 = int(rng.choice([0, 5, 0xFFFFFFF0, 0xFFFFFFFF - inflight // 2]))
+        now = int(rng.choice([100000, 0x100, 0xFFFFFFF0]))
+        acked = (rng.random(inflight) < 0.3).astype(np.uint32)
+        if big:
+            acked[:min(int(rng.choice([0, 1023, 1024, 1025, 2049, inflight - 1, inflight])), inflight)] = 1
+        sent = ((now - rng.integers(0, 1200, inflight)) & M.M32).astype(np.uint32)
+        total = max(inflight - 1, 0) * M.MAXP + int(rng.integers(1, M.MAXP + 1)) if inflight else 0
+        src = O.synth_fill_np(total, start_byte=trace)
+        for batch in range(3):
+            seqs, kind, ring, rl = _ack_batch(rng, seq0, inflight, 60 if big else 30)
+            ok, hit, acked2, counts = M.ingest(ring, 16, rl, mode, seq0, inflight, acked)
+            v_ok, v_hit, v_acked, v_counts = M.ingest(ring, 16, rl, mode, seq0, inflight, acked, vectorised=True)
+            assert np.array_equal(v_ok, ok) and np.array_equal(v_hit, hit) and v_hit.dtype == hit.dtype
+            assert np.array_equal(v_acked, acked2) and v_acked.dtype == acked2.dtype and v_counts == counts
+            # the classes, from the generator's own facts
+            d = (seqs.astype(np.int64) - seq0) & M.M32
+            valid = kind > 1
+            seen["bad"] += int((kind == 0).sum())
+            seen["wrong_type"] += int((kind == 1).sum())
+            seen["outside"] += int((valid & (hit == M.NOT_PLACED)).sum())
+            at_end = valid & (d == inflight) & (inflight > 0)
+            seen["edge"] += int(at_end.sum())
+            assert (hit[at_end] == (inflight if mode == M.CUMULATIVE else M.NOT_PLACED)).all()
+            marked, top = set(np.flatnonzero(acked).tolist()), 0
+            for i in np.flatnonzero(hit != M.NOT_PLACED):  # an ACK that marks nothing new
+                a = int(hit[i])
+                seen["dup"] += int(a in marked if mode == M.SELECTIVE else a <= top)
+                marked.add(a)
+                top = max(top, a)
+            seen["top_past_1024"] += int(mode == M.CUMULATIVE and top > 1024)
+            seen["lead_past_1024"] += int(counts[0] > 1024)
+            seen["lead_past_2049"] += int(counts[0] >= 2049)
+            acked = acked2
+            now = (now + int(rng.integers(0, 700))) & M.M32
+            max_sel = int(rng.choice([0, 7, 64, inflight + 3])) if big else int(rng.integers(0, inflight + 3))
+            flags = M.RETX_ALL if rng.integers(0, 4) == 0 else 0
+            build = max_sel <= 64
+            sel, dgrams, sent2, c = M.retransmit(src, total, seq0, inflight, acked, sent, now, 500, flags, max_sel, build=build)
+            v_sel, v_dgrams, v_sent, v_c = M.retransmit(src, total, seq0, inflight, acked, sent, now, 500, flags, max_sel,
+                                                        build=build, vectorised=True)
+            assert np.array_equal(v_sel, sel) and v_sel.dtype == sel.dtype and v_dgrams == dgrams and v_c == c
+            assert np.array_equal(v_sent, sent2) and v_sent.dtype == sent2.dtype
+            assert len(dgrams) == (c[0] if build else 0)
+            seen["ring_short"] += int(c[0] < c[1])
+            sent = sent2
+    # 320 traces x 3 batches x ~15 datagrams: an eighth each with a bad checksum and the wrong
+    # type; of the valid ones about a fifth fall outside a ~20-slot window and one in ~27
+    # names seq0 + inflight; a batch of 15 over 20 slots repeats itself several times
+    assert min(seen["bad"], seen["wrong_type"], seen["outside"], seen["dup"]) > 1000 and seen["edge"] > 100, seen
+    # (a cumulative batch leaves little un-ACKed, so rings shorter than the due set are rarer there)
+    assert seen["ring_short"] > 10 and seen["lead_past_1024"] > 0 and seen["lead_past_2049"] > 0, seen
+    assert seen["top_past_1024"] > 0 or mode == M.SELECTIVE, seen
+
+
+def test_payload_limit_is_in_both_paths_of_the_model():
+    """verify_limited: the oracle's verdict up to 4096 payload bytes, not ok and crc 0 above
+    (include/wtp_crc32.h); the oracle itself has no limit.  Literal and vectorised ingest
+    both take ok from it."""
+    dg, lens = M.limit_corpus(5000, 3, 22, 5, 64)
+    ring, rl = M.make_ring(dg, 5000)
+    o_ok, o_crc = O.verify_datagrams(ring, 5000, rl)
+    ok, crc = M.verify_limited(ring, 5000, rl)
+    assert sorted(set(lens.tolist())) == [0, 1, 3, 4, 255, 1456, 1457, 4095, 4096, 4097, 4984]
+    assert (o_ok[lens > 4096].sum(), ok[lens > 4096].sum()) == (4, 0) and (crc[lens > 4096] == 0).all()
+    assert np.array_equal(ok[lens <= 4096], o_ok[lens <= 4096]) and np.array_equal(crc[lens <= 4096], o_crc[lens <= 4096])
+    assert (ok[lens == 4096] == 1).sum() == 2 and (ok == 0).sum() == 6 + 3  # over the limit, and the corrupt ones below
+    for vec in (False, True):
+        m_ok, hit, acked, counts = M.ingest(ring, 5000, rl, M.SELECTIVE, 0, 64, np.zeros(64, np.uint32), vectorised=vec)
+        assert np.array_equal(m_ok, ok) and np.array_equal(hit != M.NOT_PLACED, ok != 0) and counts[1] == len(set(hit[ok != 0]))
+    short, slens = M.limit_corpus(5000, 3, 22, 5, 64, over=False)
+    assert short == [d for d, ln in zip(dg, lens) if ln <= 4096] and slens.max() == 4096
 
 
 def test_model_ok_is_the_oracles_and_hit_rules():
