@@ -54,6 +54,7 @@ def _load() -> C.CDLL:
         "wtp_crc32_batch_packed": (i32, [vp, sz, vp, vp, sz, vp, vp]),
         "wtp_crc32_verify_batch": (i32, [vp, sz, vp, sz, vp, vp, vp]),
         "wtp_build_data_packets": (i32, [vp, sz, u32, vp, sz, vp, vp]),
+        "wtp_build_data_packets_var": (i32, [vp, sz, vp, vp, sz, u32, vp, sz, vp, vp, vp]),
         "wtp_accept_data_packets": (i32, [vp, sz, vp, sz, u32, u32, vp, vp, vp, vp, vp, vp]),
         "wtp_tx_ingest_acks": (i32, [vp, sz, vp, sz, u32, u32, u32, vp, vp, vp, vp, vp]),
         "wtp_tx_work_bytes": (sz, [u32, u32]),
@@ -85,7 +86,7 @@ def _load() -> C.CDLL:
 LIB = _load()
 EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_count", "wtp_init", "wtp_device_status", "wtp_reserve_cus", "wtp_crc32",
             "wtp_crc32_batch_fixed", "wtp_crc32_batch_var", "wtp_crc32_batch_packed", "wtp_crc32_verify_batch", "wtp_build_data_packets",
-            "wtp_accept_data_packets", "wtp_tx_ingest_acks", "wtp_tx_work_bytes", "wtp_tx_build_retransmit",
+            "wtp_build_data_packets_var", "wtp_accept_data_packets", "wtp_tx_ingest_acks", "wtp_tx_work_bytes", "wtp_tx_build_retransmit",
             "wtp_rx_ack_work_bytes", "wtp_rx_build_acks",
             "wtp_crc32_combine", "wtp_crc32_concat_work_bytes", "wtp_crc32_concat", "wtp_crc32_buffer_work_bytes",
             "wtp_crc32_buffer", "wtp_crc32_host_buffer",
@@ -151,6 +152,17 @@ def build_data_packets(payloads, total_bytes: int, seq0: int, wire, wire_stride:
                        stream=None) -> None:
     _check(LIB.wtp_build_data_packets(_dptr(payloads), total_bytes, seq0, _dptr(wire), wire_stride,
                                       _dptr(wire_len), _stream(stream)), "wtp_build_data_packets")
+
+
+def build_data_packets_var(base, base_bytes: int, offsets, lengths, n: int, seq0: int, wire, wire_stride: int,
+                           wire_len=None, crc_out=None, stream=None) -> None:
+    """Fused DATA builder for mixed-length payloads (wtp_build_data_packets_var): payload i =
+    base[offsets[i] .. + lengths[i]) (u64 / u32 tensors) becomes datagram seq0 + i in slot i
+    of `wire`; wire_len (n x u32) = 16 + len and crc_out (n x u32) = the checksum, both 0
+    for an invalid entry, whose slot is left untouched."""
+    _check(LIB.wtp_build_data_packets_var(_dptr(base), base_bytes, _dptr(offsets), _dptr(lengths), n,
+                                          seq0 & 0xFFFFFFFF, _dptr(wire), wire_stride, _dptr(wire_len),
+                                          _dptr(crc_out), _stream(stream)), "wtp_build_data_packets_var")
 
 
 def accept_data_packets(dgrams, stride: int, recv_len, n: int, seq0: int, window: int, out, slot_len, ok,

@@ -164,6 +164,40 @@ int wtp_build_data_packets(const void *d_payloads, size_t total_bytes, uint32_t 
                            void *d_wire, size_t wire_stride, uint32_t *d_wire_len,
                            void *stream);
 
+/* Fused DATA packet builder for mixed-length payloads, the sender-side counterpart of what
+   wtp_accept_data_packets does for every length: payload i is d_base[d_offsets[i] ..
+   + d_lengths[i]) (the layout of wtp_crc32_batch_var).  Payloads may be in any order and
+   may overlap; offsets are full 64-bit and there is no size limit on base_bytes.  Payload
+   i is valid iff d_lengths[i] <= WTP_MAX_PAYLOAD, d_offsets[i] <= base_bytes and
+   d_lengths[i] <= base_bytes - d_offsets[i].  For a valid i, with len = d_lengths[i]:
+   d_wire[i*wire_stride .. +16) = htonl{type = 2, seqNum = seq0 + i (mod 2^32), length =
+   len, checksum = crc32(payload)} and the payload follows the header, byte-identical to
+   oracle.build_datagram(seq0 + i, payload) (oracle/oracle.py) and, for a 1456-byte
+   payload, to what wtp_build_data_packets writes; d_wire_len[i] = 16 + len and
+   d_crc_out[i] = the checksum.  len == 0 is valid (checksum 0, wire length 16).  For an invalid i the slot
+   is not written at all, d_wire_len[i] = 0 and d_crc_out[i] = 0; no status flag is set
+   (as in wtp_tx_ingest_acks), so with d_wire_len == NULL nothing reports an invalid
+   entry.  Nothing else is written: bytes [16 + len, wire_stride) of every slot and
+   everything outside [d_wire, d_wire + n*wire_stride) stay as they were; d_base,
+   d_offsets and d_lengths are only read, and no byte outside [d_base, d_base +
+   base_bytes) is ever loaded, by the widened and aligned-down vector loads and for
+   invalid payloads too (a vector at an edge of the buffer is loaded bytewise).  d_wire
+   overlapping d_base is undefined.  d_wire_len and d_crc_out may be NULL.  n == 0 is
+   valid and launches nothing.  WTP_EINVAL (before any device is touched): wire_stride <
+   1472, n >= 2^31, a NULL d_base, d_offsets, d_lengths or d_wire with n > 0.  One
+   stream-ordered launch with no host synchronisation, no allocation and no scratch; the
+   call uses no memory besides the caller's buffers and keeps no state.  It reads no
+   library table, so it needs no wtp_init before a capture; graph captures, replays and
+   concurrent calls are independent.  wtp_last_kernel() names "k_build_var".  Fast path
+   (16-B vector stores, each payload byte read once: the kernel hashes what it copies): a
+   16-B aligned d_wire with wire_stride % 16 == 0, and any source alignment (packed
+   payloads sit at arbitrary byte addresses); other wire alignments are built bytewise,
+   exactly. */
+int wtp_build_data_packets_var(const void *d_base, size_t base_bytes,
+                               const uint64_t *d_offsets, const uint32_t *d_lengths, size_t n,
+                               uint32_t seq0, void *d_wire, size_t wire_stride,
+                               uint32_t *d_wire_len, uint32_t *d_crc_out, void *stream);
+
 /* Device-side receive, the inverse of wtp_build_data_packets: verify, window-place and
    ACK a batch of datagrams (cpp/src/base/Receiver.cpp:25-35 payload memcpy + :208-237
    window check, buffering, next_seq).  Datagrams as in wtp_crc32_verify_batch.  The
