@@ -61,6 +61,8 @@ def _load() -> C.CDLL:
         "wtp_tx_build_retransmit": (i32, [vp, sz, u32, u32, vp, vp, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, sz, vp]),
         "wtp_rx_ack_work_bytes": (sz, [sz, u32, u32]),
         "wtp_rx_build_acks": (i32, [vp, sz, vp, sz, u32, u32, u32, vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, sz, vp]),
+        "wtp_rx_deliver_work_bytes": (sz, [u32]),
+        "wtp_rx_deliver": (i32, [vp, vp, u32, u32, vp, sz, u64, vp, vp, vp, vp, sz, vp]),
         "wtp_crc32_combine": (u32, [u32, u32, u64]),
         "wtp_crc32_concat_work_bytes": (sz, [sz]),
         "wtp_crc32_concat": (i32, [vp, vp, u64, u64, sz, vp, sz, vp, vp]),
@@ -87,7 +89,7 @@ LIB = _load()
 EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_count", "wtp_init", "wtp_device_status", "wtp_reserve_cus", "wtp_crc32",
             "wtp_crc32_batch_fixed", "wtp_crc32_batch_var", "wtp_crc32_batch_packed", "wtp_crc32_verify_batch", "wtp_build_data_packets",
             "wtp_build_data_packets_var", "wtp_accept_data_packets", "wtp_tx_ingest_acks", "wtp_tx_work_bytes", "wtp_tx_build_retransmit",
-            "wtp_rx_ack_work_bytes", "wtp_rx_build_acks",
+            "wtp_rx_ack_work_bytes", "wtp_rx_build_acks", "wtp_rx_deliver_work_bytes", "wtp_rx_deliver",
             "wtp_crc32_combine", "wtp_crc32_concat_work_bytes", "wtp_crc32_concat", "wtp_crc32_buffer_work_bytes",
             "wtp_crc32_buffer", "wtp_crc32_host_buffer",
             "wtp_crc32_host_batch_fixed", "wtp_crc32_host_chunked", "wtp_crc32_host_chunked_multi", "wtp_crc32_host_verify",
@@ -219,6 +221,24 @@ def rx_build_acks(dgrams, stride: int, recv_len, n: int, mode: int, seq0: int, w
     _check(LIB.wtp_rx_build_acks(_dptr(dgrams), stride, _dptr(recv_len), n, mode, seq0 & 0xFFFFFFFF, window, _dptr(ok),
                                  _dptr(place), _dptr(slot_len), _dptr(ack_wire), ack_stride, skip, max_acks,
                                  _dptr(src), _dptr(counts), wp, wb, _stream(stream)), "wtp_rx_build_acks")
+
+
+# ---- in-order flush of the window ------------------------------------------------------
+def rx_deliver_work_bytes(window: int) -> int:
+    return int(LIB.wtp_rx_deliver_work_bytes(window))
+
+
+def rx_deliver(img, slot_len, window: int, max_slots: int, stream_buf, stream_bytes: int, stream_off: int,
+               offsets_out, lengths_out, counts, work=None, stream=None) -> None:
+    """The window's in-order prefix as a packed stream (wtp_rx_deliver): `img` / `slot_len` are
+    accept's window state; the first k leading filled slots (k <= max_slots, whole records
+    that fit stream_bytes) go back to back to `stream_buf` from byte stream_off on, their
+    offsets (u64) and lengths (u32) to offsets_out / lengths_out (either may be None);
+    counts (4 x u64) = (k, run, bytes delivered, bytes the whole run needs)."""
+    work, wp, wb = _work(work, rx_deliver_work_bytes(window))
+    _check(LIB.wtp_rx_deliver(_dptr(img), _dptr(slot_len), window, max_slots, _dptr(stream_buf), stream_bytes,
+                              stream_off, _dptr(offsets_out), _dptr(lengths_out), _dptr(counts), wp, wb,
+                              _stream(stream)), "wtp_rx_deliver")
 
 
 # ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------

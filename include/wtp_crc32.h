@@ -364,7 +364,7 @@ int wtp_tx_build_retransmit(const void *d_payloads, size_t total_bytes, uint32_t
    are sized from n and window.  The call keeps no state and reads no library table, so it
    needs no wtp_init before a capture, and concurrent calls on different work buffers are
    independent.  wtp_last_kernel() names "k_ack_emit". */
-#define WTP_RX_MAX_WINDOW (1u << 20)   /* cumulative mode only */
+#define WTP_RX_MAX_WINDOW (1u << 20)   /* cumulative mode only; wtp_rx_deliver */
 #define WTP_RX_MAX_BATCH  (1u << 24)
 size_t wtp_rx_ack_work_bytes(size_t n, uint32_t window, uint32_t mode);
 int wtp_rx_build_acks(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len, size_t n,
@@ -373,6 +373,63 @@ int wtp_rx_build_acks(const void *d_dgrams, size_t stride, const uint32_t *d_rec
                       void *d_ack_wire, size_t ack_stride, uint32_t skip, uint32_t max_acks,
                       uint32_t *d_src, uint32_t *d_counts,
                       void *d_work, size_t work_bytes, void *stream);
+
+/* ---- in-order flush: the window's leading run as a packed stream ---------------------
+   The sixth call of the protocol loop (cpp/src/base/Receiver.cpp:208-237, the in-order
+   flush; wReceiver.cpp's std::map loop): it follows wtp_accept_data_packets and
+   wtp_rx_build_acks and turns the in-order prefix of the window back into the byte stream
+   the sender started from, in the (base, offsets, lengths) layout of wtp_crc32_batch_var, so
+   that packed records -> wtp_build_data_packets_var -> channel -> wtp_accept_data_packets
+   -> wtp_rx_deliver gives the same packed records, and wtp_crc32_batch_packed,
+   wtp_crc32_buffer and wtp_crc32_concat apply to the output directly.
+
+   d_img and d_slot_len are accept's window state (its d_out and d_slot_len), passed already
+   offset to the current window base: slot s = d_img[s*1456 .. +1456), d_slot_len[s] its
+   stored length or WTP_SLOT_EMPTY.  run = the number of leading slots with d_slot_len[s] <=
+   WTP_MAX_PAYLOAD: any larger value (WTP_SLOT_EMPTY, a claim pattern 0x80000000 | i,
+   anything else) ends the run, so every input is defined and nothing is indexed by a bad
+   length.  P_s = the sum of d_slot_len[t] for t < s (64-bit).  k = the largest value with k
+   <= min(run, max_slots) and stream_off + P_k <= stream_bytes: whole records only, and
+   zero-length records that still fit are included.  For s < k, with len = d_slot_len[s]:
+   d_stream[stream_off + P_s .. + len) = d_img[s*1456 .. + len), d_offsets_out[s] =
+   stream_off + P_s and d_lengths_out[s] = len.  d_counts[0] = k, d_counts[1] = run,
+   d_counts[2] = P_k (the bytes delivered), d_counts[3] = P_run (the bytes the whole run
+   needs: a caller whose buffer was too small sizes the next one from it).  d_counts is
+   always written, also for window == 0 and max_slots == 0, which are both valid; with
+   max_slots == 0, run and P_run are still reported.
+
+   Nothing else is written: every byte of d_stream outside [stream_off, stream_off + P_k)
+   stays as it was, the bytes that share a 16-B vector with the first and the last
+   delivered byte included (no read-modify-write of neighbouring bytes); entries >= k of
+   d_offsets_out and d_lengths_out stay as they were; d_img and d_slot_len are only read
+   (the caller resets or shifts them when it advances the window by k, as today), and no
+   byte outside [d_img, d_img + window*1456) is ever loaded, by the widened and aligned-down
+   vector loads at the image's two ends too.  d_stream overlapping d_img is undefined.
+   d_offsets_out and d_lengths_out may be NULL.
+
+   WTP_EINVAL (before any device is touched): window > WTP_RX_MAX_WINDOW (so P < 2^31),
+   stream_off > stream_bytes, work_bytes < wtp_rx_deliver_work_bytes(window), a NULL d_counts
+   or d_work, a NULL d_img or d_slot_len with window > 0, a NULL d_stream with window > 0
+   and max_slots > 0.
+
+   d_work is the caller's scratch as for wtp_rx_build_acks (any alignment, contents
+   arbitrary on entry, unspecified on return, no allocation by the library; every word the
+   call reads it has written before).  wtp_rx_deliver_work_bytes is monotone and at most
+   64 KiB + 8 bytes per window slot.  Fast path (one 16-B store per 16 stream bytes whatever
+   the stream's byte phase, the source loaded as dwords and shifted): a 4-B aligned d_img;
+   a vector that spans records, the first and last vector of the delivered range, a vector
+   at the image's end and any other image alignment are gathered bytewise, exactly.
+   Stream-ordered launches (block sums, scan, copy) with no host synchronisation: d_counts is
+   never read on the host, grids are sized from window and max_slots.  No allocation and no
+   library table, so no wtp_init is needed before a capture; graph captures, replays and
+   concurrent calls on different work buffers are independent.  wtp_last_kernel() names
+   "k_deliver_copy" (or "k_deliver_scan" when window or max_slots is 0 and nothing can be
+   copied). */
+size_t wtp_rx_deliver_work_bytes(uint32_t window);
+int wtp_rx_deliver(const void *d_img, const uint32_t *d_slot_len, uint32_t window, uint32_t max_slots,
+                   void *d_stream, size_t stream_bytes, uint64_t stream_off,
+                   uint64_t *d_offsets_out, uint32_t *d_lengths_out, uint64_t *d_counts,
+                   void *d_work, size_t work_bytes, void *stream);
 
 /* ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------
    The reference's crc32(buf, size) takes any size; these give it for device-resident data
