@@ -63,6 +63,8 @@ def _load() -> C.CDLL:
         "wtp_rx_build_acks": (i32, [vp, sz, vp, sz, u32, u32, u32, vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, sz, vp]),
         "wtp_rx_deliver_work_bytes": (sz, [u32]),
         "wtp_rx_deliver": (i32, [vp, vp, u32, u32, vp, sz, u64, vp, vp, vp, vp, sz, vp]),
+        "wtp_rx_advance": (i32, [vp, vp, u32, vp, vp, vp, vp]),
+        "wtp_tx_advance": (i32, [vp, vp, u32, vp, u32, vp, vp, vp]),
         "wtp_crc32_combine": (u32, [u32, u32, u64]),
         "wtp_crc32_concat_work_bytes": (sz, [sz]),
         "wtp_crc32_concat": (i32, [vp, vp, u64, u64, sz, vp, sz, vp, vp]),
@@ -90,6 +92,7 @@ EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_coun
             "wtp_crc32_batch_fixed", "wtp_crc32_batch_var", "wtp_crc32_batch_packed", "wtp_crc32_verify_batch", "wtp_build_data_packets",
             "wtp_build_data_packets_var", "wtp_accept_data_packets", "wtp_tx_ingest_acks", "wtp_tx_work_bytes", "wtp_tx_build_retransmit",
             "wtp_rx_ack_work_bytes", "wtp_rx_build_acks", "wtp_rx_deliver_work_bytes", "wtp_rx_deliver",
+            "wtp_rx_advance", "wtp_tx_advance",
             "wtp_crc32_combine", "wtp_crc32_concat_work_bytes", "wtp_crc32_concat", "wtp_crc32_buffer_work_bytes",
             "wtp_crc32_buffer", "wtp_crc32_host_buffer",
             "wtp_crc32_host_batch_fixed", "wtp_crc32_host_chunked", "wtp_crc32_host_chunked_multi", "wtp_crc32_host_verify",
@@ -239,6 +242,24 @@ def rx_deliver(img, slot_len, window: int, max_slots: int, stream_buf, stream_by
     _check(LIB.wtp_rx_deliver(_dptr(img), _dptr(slot_len), window, max_slots, _dptr(stream_buf), stream_bytes,
                               stream_off, _dptr(offsets_out), _dptr(lengths_out), _dptr(counts), wp, wb,
                               _stream(stream)), "wtp_rx_deliver")
+
+
+# ---- sliding both windows --------------------------------------------------------------
+def rx_advance(img, slot_len, window: int, adv, img_next, slot_len_next, stream=None) -> None:
+    """Slide the receive window (wtp_rx_advance): `img` / `slot_len` move down by min(adv[0],
+    window) slots into `img_next` / `slot_len_next`, EMPTY behind them; `adv` is a u64 device
+    tensor read when the kernel runs (rx_deliver's counts as they are).  Both images may be
+    None: then only slot_len moves."""
+    _check(LIB.wtp_rx_advance(_dptr(img), _dptr(slot_len), window, _dptr(adv), _dptr(img_next), _dptr(slot_len_next),
+                              _stream(stream)), "wtp_rx_advance")
+
+
+def tx_advance(acked, sent_ms, slots: int, adv, fill_ms: int, acked_next, sent_ms_next, stream=None) -> None:
+    """Slide the sender window (wtp_tx_advance): `acked` / `sent_ms` (slots x u32) move down by
+    min(adv[0], slots) entries into `acked_next` / `sent_ms_next`, 0 / fill_ms behind them;
+    `adv` is a u32 device tensor read when the kernel runs (tx_ingest_acks' counts)."""
+    _check(LIB.wtp_tx_advance(_dptr(acked), _dptr(sent_ms), slots, _dptr(adv), fill_ms & 0xFFFFFFFF, _dptr(acked_next),
+                              _dptr(sent_ms_next), _stream(stream)), "wtp_tx_advance")
 
 
 # ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------

@@ -204,7 +204,8 @@ int wtp_build_data_packets_var(const void *d_base, size_t base_bytes,
    caller owns the window state, which persists across calls: d_out, window * 1456 bytes,
    the file image from chunk seq0 on (slot s = bytes [s*1456, (s+1)*1456)), and
    d_slot_len[window], WTP_SLOT_EMPTY for an empty slot, else the payload length stored
-   in it (set it to 0xFF bytes once; shift or reset it when the window advances).
+   in it (set it to 0xFF bytes once; shift or reset it when the window advances:
+   wtp_rx_advance below does that on the device).
    The result equals processing the datagrams one by one in index (arrival) order:
    d_ok[i] is what wtp_crc32_verify_batch writes.  Datagram i is placed iff d_ok[i],
    ntohl(type) == WTP_TYPE_DATA, len = recv_len - 16 <= WTP_MAX_PAYLOAD,
@@ -238,7 +239,8 @@ int wtp_accept_data_packets(const void *d_dgrams, size_t stride, const uint32_t 
    points at the first byte of chunk seq0 and total_bytes is the number of file bytes from
    there on: slot s holds min(1456, total_bytes - s*1456) bytes.  When the window advances
    by a, the caller shifts d_acked and d_sent_ms by a and moves d_payloads, total_bytes and
-   seq0.  inflight <= WTP_TX_MAX_INFLIGHT.
+   seq0.  wtp_tx_advance below does that shift on the device.  inflight <=
+   WTP_TX_MAX_INFLIGHT.
 
    wtp_tx_ingest_acks turns a batch of received datagrams (laid out as in
    wtp_crc32_verify_batch) into window state.  d_ok[i] is what wtp_crc32_verify_batch
@@ -402,7 +404,8 @@ int wtp_rx_build_acks(const void *d_dgrams, size_t stride, const uint32_t *d_rec
    stays as it was, the bytes that share a 16-B vector with the first and the last
    delivered byte included (no read-modify-write of neighbouring bytes); entries >= k of
    d_offsets_out and d_lengths_out stay as they were; d_img and d_slot_len are only read
-   (the caller resets or shifts them when it advances the window by k, as today), and no
+   (the caller resets or shifts them when it advances the window by k, as today;
+   wtp_rx_advance below takes d_counts as it is and does that on the device), and no
    byte outside [d_img, d_img + window*1456) is ever loaded, by the widened and aligned-down
    vector loads at the image's two ends too.  d_stream overlapping d_img is undefined.
    d_offsets_out and d_lengths_out may be NULL.
@@ -430,6 +433,70 @@ int wtp_rx_deliver(const void *d_img, const uint32_t *d_slot_len, uint32_t windo
                    void *d_stream, size_t stream_bytes, uint64_t stream_off,
                    uint64_t *d_offsets_out, uint32_t *d_lengths_out, uint64_t *d_counts,
                    void *d_work, size_t work_bytes, void *stream);
+
+/* ---- sliding both windows: the end of a round ------------------------------------------
+   The six calls above each handle one batch against a window that is fixed for that batch;
+   these two move the window.  A receive round is accept -> ACKs -> deliver -> advance, all
+   stream-ordered with one host read at the end, and a transfer of any length runs in two
+   windows' worth of state.  Both calls write a second copy of the state: the caller keeps
+   two sets of buffers and swaps them each round (an in-place slide would make every slot
+   both a source and a destination of workgroups that run in no defined order).
+
+   wtp_rx_advance slides accept's window state (d_img, window * 1456 bytes, and d_slot_len,
+   as in wtp_rx_deliver) down by a slots into d_img_next / d_slot_len_next.  d_adv points at
+   one device-resident uint64_t, read on the device when the kernel runs, not when the call is
+   made: wtp_rx_deliver's d_counts can be passed as it is (d_counts[0] = k) with no host read
+   in between, and one captured graph serves every round.  a = min(*d_adv, window), compared
+   in 64 bits, so any value of *d_adv is defined.  For every s in [0, window), with t = s + a
+   and v = d_slot_len[t] if t < window, else WTP_SLOT_EMPTY: d_slot_len_next[s] = v, for
+   every v (a value above WTP_MAX_PAYLOAD, that is WTP_SLOT_EMPTY, a claim pattern or anything
+   else, is carried unchanged and nothing is copied for it); and if v <= WTP_MAX_PAYLOAD and
+   the images are given, d_img_next[s*1456 .. + v) = d_img[t*1456 .. + v).  Nothing else is
+   written: bytes [v, 1456) of slot s in d_img_next stay as they were (accept's rule for a
+   placed slot), a slot that receives no record stays whole, and no byte outside [d_img_next,
+   d_img_next + window*1456) or [d_slot_len_next, + 4*window) is written.  d_img, d_slot_len
+   and *d_adv are only read, and no byte outside [d_img, d_img + window*1456) is ever loaded,
+   by the vector loads at the image's two ends too.  d_img and d_img_next may both be NULL:
+   then only d_slot_len moves (a fixed-chunk transfer, where the image already is the file
+   and the caller moves a pointer, not bytes).  window == 0 is valid and launches nothing.
+
+   WTP_EINVAL (before any device is touched), each with its own message: window >
+   WTP_RX_MAX_WINDOW; exactly one of d_img and d_img_next NULL; a NULL d_adv, d_slot_len or
+   d_slot_len_next with window > 0; [d_slot_len, + 4*window) overlapping [d_slot_len_next,
+   + 4*window); [d_img, + 1456*window) overlapping [d_img_next, + 1456*window).  Ranges that
+   touch without sharing a byte are valid.
+
+   One stream-ordered launch with no host synchronisation, no allocation, no scratch and no
+   library table, so no wtp_init is needed before a capture; graph captures, replays and
+   concurrent calls on different windows are independent.  wtp_last_kernel() names
+   "k_rx_advance".  Fast path (16-B vectors): both images 16-B aligned (1456 = 91 * 16, so
+   every slot then is); the v % 16 tail, and every other image alignment, move bytewise,
+   exactly, and no access is wider than the alignment allows.  The cost follows the bytes
+   that are filled, not the window: an empty slot costs the 4 + 4 bytes of its length. */
+int wtp_rx_advance(const void *d_img, const uint32_t *d_slot_len, uint32_t window,
+                   const uint64_t *d_adv,
+                   void *d_img_next, uint32_t *d_slot_len_next, void *stream);
+
+/* wtp_tx_advance slides the sender window's state (d_acked, d_sent_ms of
+   wtp_tx_ingest_acks / wtp_tx_build_retransmit) down by a entries into d_acked_next /
+   d_sent_ms_next.  slots is the number of entries of each of the four arrays, the caller's
+   window capacity, which may be larger than the current inflight; slots <=
+   WTP_TX_MAX_INFLIGHT.  d_adv points at one device-resident uint32_t, read when the kernel
+   runs: wtp_tx_ingest_acks' d_counts can be passed as it is (d_counts[0] = the advance);
+   wtp_tx_build_retransmit writes its own d_counts, so a caller that runs it before the
+   advance gives the two calls separate buffers.  a = min(*d_adv, slots).  For s < slots
+   with t = s + a: d_acked_next[s] = d_acked[t] if t < slots, else 0, and d_sent_ms_next[s] =
+   d_sent_ms[t] if t < slots, else fill_ms (any value; the entries behind the shifted ones
+   belong to packets not sent yet).  The inputs and *d_adv are only read; nothing outside
+   the two output arrays is written.  slots == 0 is valid and launches nothing.  WTP_EINVAL
+   (before any device is touched): slots > WTP_TX_MAX_INFLIGHT, a NULL pointer with slots >
+   0, an output array overlapping an input array or the other output (arrays that touch
+   are valid).  One stream-ordered launch, one lane per entry; no host synchronisation,
+   allocation, scratch or library table, and the same independence of captures, replays and
+   concurrent calls as wtp_rx_advance.  wtp_last_kernel() names "k_tx_advance". */
+int wtp_tx_advance(const uint32_t *d_acked, const uint32_t *d_sent_ms, uint32_t slots,
+                   const uint32_t *d_adv, uint32_t fill_ms,
+                   uint32_t *d_acked_next, uint32_t *d_sent_ms_next, void *stream);
 
 /* ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------
    The reference's crc32(buf, size) takes any size; these give it for device-resident data
