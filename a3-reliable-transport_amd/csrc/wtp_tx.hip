@@ -1,5 +1,5 @@
 // wtp_tx.hip — device-side sender window (include/wtp_crc32.h: wtp_tx_ingest_acks,
-// wtp_tx_build_retransmit), the mirror of wtp_accept.hip.
+// wtp_tx_build_retransmit, wtp_tx_build_retransmit_var), the mirror of wtp_accept.hip.
 //
 // The window state (d_acked[inflight], d_sent_ms[inflight]) is the caller's and persists
 // across calls.  Semantics: the reference's selective-repeat sender, cpp/src/opt/
@@ -44,6 +44,12 @@
 //                   profiles/retx/retx_bench_twopass.json).
 //                   A chunk shorter than 1456 B (at most the window's last) and buffers
 //                   that are not 16-B aligned go bytewise, same segments, same result.
+// wtp_tx_build_retransmit_var, the same window over records of mixed length (base, offsets,
+// lengths: wtp_build_data_packets_var's layout), the same d_work:
+//   k_tx_count, k_tx_select   as above, unchanged: the selection does not look at the records
+//   k_tx_emit_var   wtp_txvar.hip, its own translation unit so that the kernels here keep
+//                   their machine code: the builder's move-and-hash body behind the
+//                   selection, launched through tx_emit_var_launch.
 // The selection is ordered because the reference walks its deque front to back, and a
 // ring shorter than the due set must hold the oldest packets; it is counted on the device
 // because the host never reads d_counts[0]: grids are sized from max_sel.
@@ -348,6 +354,13 @@ k_tx_emit(const uint8_t *__restrict__ pay, uint64_t total_bytes, uint32_t seq0, 
 }  // namespace dev
 }  // namespace wtp
 
+namespace wtp {
+// wtp_txvar.hip: k_tx_emit_var over the selection picked[m] (m > 0) that k_tx_select left
+int tx_emit_var_launch(const void *d_base, size_t base_bytes, const uint64_t *d_offsets, const uint32_t *d_lengths,
+                       uint32_t seq0, const uint32_t *picked, const uint32_t *d_counts, uint32_t m, void *d_wire,
+                       size_t wire_stride, uint32_t *d_wire_len, uint32_t *d_crc_out, hipStream_t st);
+}  // namespace wtp
+
 namespace {
 
 // d_work of wtp_tx_build_retransmit, from align4 on: picked[m], blk[blocks];
@@ -440,4 +453,38 @@ extern "C" int wtp_tx_build_retransmit(const void *d_payloads, size_t total_byte
                        d_wire_len);
     wtp_set_kernel_("k_tx_emit");
     return launch_check("k_tx_emit");
+}
+
+extern "C" int wtp_tx_build_retransmit_var(const void *d_base, size_t base_bytes, const uint64_t *d_offsets,
+                                           const uint32_t *d_lengths, uint32_t seq0, uint32_t inflight,
+                                           const uint32_t *d_acked, uint32_t *d_sent_ms, uint32_t now_ms,
+                                           uint32_t timeout_ms, uint32_t flags, void *d_wire, size_t wire_stride,
+                                           uint32_t max_sel, uint32_t *d_sel, uint32_t *d_wire_len, uint32_t *d_crc_out,
+                                           uint32_t *d_counts, void *d_work, size_t work_bytes, void *stream) {
+    using namespace wtp;
+    if (wire_stride < WTP_HEADER_BYTES + WTP_MAX_PAYLOAD) return fail(WTP_EINVAL, "wire_stride %zu < 1472", wire_stride);
+    if (inflight > WTP_TX_MAX_INFLIGHT) return fail(WTP_EINVAL, "inflight %u > %u", inflight, WTP_TX_MAX_INFLIGHT);
+    const TxWork w = tx_layout(inflight, max_sel);
+    if (work_bytes < w.bytes) return fail(WTP_EINVAL, "work_bytes %zu < %zu", work_bytes, w.bytes);
+    if (!d_counts || !d_work) return fail(WTP_EINVAL, "null pointer: d_counts or d_work");
+    if (inflight > 0 && (!d_base || !d_offsets || !d_lengths || !d_acked || !d_sent_ms))
+        return fail(WTP_EINVAL, "null pointer: d_base, d_offsets, d_lengths, d_acked or d_sent_ms");
+    if (w.m > 0 && !d_wire) return fail(WTP_EINVAL, "null pointer: d_wire");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint8_t *work = align4(d_work);
+    uint32_t *picked = reinterpret_cast<uint32_t *>(work + w.picked);
+    uint32_t *blk = reinterpret_cast<uint32_t *>(work + w.blk);
+    int rc = WTP_OK;
+    if (w.blocks > 0) {
+        hipLaunchKernelGGL(dev::k_tx_count, dim3(w.blocks), dim3(dev::kTxBlock), 0, st, d_acked, d_sent_ms, inflight,
+                           now_ms, timeout_ms, flags, blk);
+        if ((rc = launch_check("k_tx_count"))) return rc;
+    }
+    // inflight == 0: one block, which only writes d_counts = {0, 0}
+    hipLaunchKernelGGL(dev::k_tx_select, dim3(std::max(w.blocks, 1u)), dim3(dev::kTxBlock), 0, st, d_acked, d_sent_ms,
+                       inflight, now_ms, timeout_ms, flags, blk, w.blocks, w.m, d_sel, picked, d_counts);
+    wtp_set_kernel_("k_tx_select");
+    if ((rc = launch_check("k_tx_select")) || w.m == 0) return rc;
+    return tx_emit_var_launch(d_base, base_bytes, d_offsets, d_lengths, seq0, picked, d_counts, w.m, d_wire, wire_stride,
+                              d_wire_len, d_crc_out, st);
 }

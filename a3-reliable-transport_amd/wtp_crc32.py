@@ -59,6 +59,8 @@ def _load() -> C.CDLL:
         "wtp_tx_ingest_acks": (i32, [vp, sz, vp, sz, u32, u32, u32, vp, vp, vp, vp, vp]),
         "wtp_tx_work_bytes": (sz, [u32, u32]),
         "wtp_tx_build_retransmit": (i32, [vp, sz, u32, u32, vp, vp, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, sz, vp]),
+        "wtp_tx_build_retransmit_var": (i32, [vp, sz, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, sz, u32, vp, vp, vp, vp, vp,
+                                              sz, vp]),
         "wtp_rx_ack_work_bytes": (sz, [sz, u32, u32]),
         "wtp_rx_build_acks": (i32, [vp, sz, vp, sz, u32, u32, u32, vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, sz, vp]),
         "wtp_rx_deliver_work_bytes": (sz, [u32]),
@@ -91,7 +93,7 @@ LIB = _load()
 EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_count", "wtp_init", "wtp_device_status", "wtp_reserve_cus", "wtp_crc32",
             "wtp_crc32_batch_fixed", "wtp_crc32_batch_var", "wtp_crc32_batch_packed", "wtp_crc32_verify_batch", "wtp_build_data_packets",
             "wtp_build_data_packets_var", "wtp_accept_data_packets", "wtp_tx_ingest_acks", "wtp_tx_work_bytes", "wtp_tx_build_retransmit",
-            "wtp_rx_ack_work_bytes", "wtp_rx_build_acks", "wtp_rx_deliver_work_bytes", "wtp_rx_deliver",
+            "wtp_tx_build_retransmit_var", "wtp_rx_ack_work_bytes", "wtp_rx_build_acks", "wtp_rx_deliver_work_bytes", "wtp_rx_deliver",
             "wtp_rx_advance", "wtp_tx_advance",
             "wtp_crc32_combine", "wtp_crc32_concat_work_bytes", "wtp_crc32_concat", "wtp_crc32_buffer_work_bytes",
             "wtp_crc32_buffer", "wtp_crc32_host_buffer",
@@ -205,6 +207,21 @@ def tx_build_retransmit(payloads, total_bytes: int, seq0: int, inflight: int, ac
                                        _dptr(sent_ms), now_ms & 0xFFFFFFFF, timeout_ms, flags, _dptr(wire),
                                        wire_stride, max_sel, _dptr(sel), _dptr(wire_len), _dptr(counts), wp, wb,
                                        _stream(stream)), "wtp_tx_build_retransmit")
+
+
+def tx_build_retransmit_var(base, base_bytes: int, offsets, lengths, seq0: int, inflight: int, acked, sent_ms,
+                            now_ms: int, timeout_ms: int, flags: int, wire, wire_stride: int, max_sel: int, sel=None,
+                            wire_len=None, crc_out=None, counts=None, work=None, stream=None) -> None:
+    """tx_build_retransmit over records of mixed length (wtp_tx_build_retransmit_var): slot s
+    of the window is base[offsets[s] .. + lengths[s]) (u64 / u32 tensors, already advanced to
+    the window base); the same selection, then entry k = the datagram of (seq0 + sel[k],
+    record sel[k]) as build_data_packets_var builds it; wire_len / crc_out (u32) are 0 for an
+    invalid record, whose slot is left untouched; counts (2 x u32) = (emitted, due)."""
+    work, wp, wb = _work(work, tx_work_bytes(inflight, max_sel))
+    _check(LIB.wtp_tx_build_retransmit_var(_dptr(base), base_bytes, _dptr(offsets), _dptr(lengths), seq0 & 0xFFFFFFFF,
+                                           inflight, _dptr(acked), _dptr(sent_ms), now_ms & 0xFFFFFFFF, timeout_ms, flags,
+                                           _dptr(wire), wire_stride, max_sel, _dptr(sel), _dptr(wire_len), _dptr(crc_out),
+                                           _dptr(counts), wp, wb, _stream(stream)), "wtp_tx_build_retransmit_var")
 
 
 # ---- device-side ACK generation --------------------------------------------------------

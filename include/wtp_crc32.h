@@ -308,6 +308,63 @@ int wtp_tx_build_retransmit(const void *d_payloads, size_t total_bytes, uint32_t
                             uint32_t *d_sel, uint32_t *d_wire_len, uint32_t *d_counts,
                             void *d_work, size_t work_bytes, void *stream);
 
+/* wtp_tx_build_retransmit_var is wtp_tx_build_retransmit for records of mixed length, in the
+   layout of wtp_crc32_batch_var and wtp_build_data_packets_var (base, offsets, lengths).
+   The window state (d_acked, d_sent_ms, seq0, inflight, the due rule, flags) is exactly
+   that of wtp_tx_build_retransmit.  Slot s in [0, inflight) is the record d_base[
+   d_offsets[s] .. + d_lengths[s]).  d_offsets and d_lengths are passed already advanced to
+   the window base: when the window advances by a, the caller adds a to the two pointers
+   and to seq0.  d_base and base_bytes stay the whole buffer: they bound the loads, as in
+   wtp_build_data_packets_var.  No entry at or above inflight of either array is read.
+   Offsets are full 64-bit, records may be in any order and may overlap, and there is no
+   size limit on base_bytes.
+   Selection is that of wtp_tx_build_retransmit, word for word: slot s is due iff
+   d_acked[s] == 0 and (flags & WTP_RETX_ALL or (uint32_t)(now_ms - d_sent_ms[s]) >
+   timeout_ms); due slots are taken in rising slot order and the first min(due, max_sel) of
+   them are emitted, entry k gets d_sel[k] = s and d_sent_ms[s] = now_ms; d_counts[0] = the
+   number emitted, d_counts[1] = the number due.  The selection does not look at the
+   records: a due slot whose record is invalid is still selected, still counted and still
+   gets its timer reset.
+   Emit: entry k with s = d_sel[k] follows wtp_build_data_packets_var's rule for one
+   payload.  It is valid iff len = d_lengths[s] <= WTP_MAX_PAYLOAD, off = d_offsets[s] <=
+   base_bytes and len <= base_bytes - off.  A valid entry writes d_wire[k*wire_stride ..) =
+   htonl{type = 2, seqNum = seq0 + s (mod 2^32), length = len, checksum = crc32(payload)}
+   || payload, d_wire_len[k] = 16 + len and d_crc_out[k] = the checksum.  The datagram is
+   byte-identical to oracle.build_datagram(seq0 + s, payload) (oracle/oracle.py), to what
+   wtp_build_data_packets_var writes for that record and, for a 1456-byte chunk, to what
+   wtp_tx_build_retransmit writes.  len == 0 is valid (checksum 0, wire length 16).  For an
+   invalid entry the slot is not written at all, d_wire_len[k] = 0 and d_crc_out[k] = 0.
+   Nothing else is written: entries k >= d_counts[0] of d_wire, d_sel, d_wire_len and
+   d_crc_out, bytes [16 + len, wire_stride) of every slot and the timers of slots not
+   emitted stay as they were; d_base, d_offsets, d_lengths and d_acked are only read, and
+   no byte outside [d_base, d_base + base_bytes) is ever loaded (a vector at an edge of the
+   buffer is loaded bytewise, as in the builder).  d_wire overlapping d_base is undefined.
+   d_sel, d_wire_len and d_crc_out may be NULL.  inflight == 0 and max_sel == 0 are valid:
+   d_counts is still written.
+   WTP_EINVAL (before any device is touched, each with its own message): wire_stride <
+   1472, inflight > WTP_TX_MAX_INFLIGHT, work_bytes < wtp_tx_work_bytes(inflight, max_sel)
+   (the same function and the same scratch contract as wtp_tx_build_retransmit), a NULL
+   d_counts or d_work, a NULL d_base, d_offsets, d_lengths, d_acked or d_sent_ms with
+   inflight > 0, a NULL d_wire with inflight > 0 and max_sel > 0.  There is no total_bytes
+   check: validity is per record, on the device.
+   Stream-ordered launches (count, select, emit) with no host synchronisation and no
+   allocation: d_counts[0] is never read on the host, grids are sized from max_sel (the
+   emit kernel reads the count on the device and spreads the emitted datagrams over its
+   grid, so a small due set costs the same in a large ring as in a fitted one).  The call
+   reads no library table, so it needs no wtp_init before a capture; captures, replays and
+   concurrent calls on different work buffers are independent.  wtp_last_kernel() names
+   "k_tx_emit_var" (or "k_tx_select" when max_sel or inflight is 0).  Fast path: a 16-B
+   aligned d_wire with wire_stride % 16 == 0 and any source alignment; other wire
+   alignments are built bytewise, exactly. */
+int wtp_tx_build_retransmit_var(const void *d_base, size_t base_bytes,
+                                const uint64_t *d_offsets, const uint32_t *d_lengths,
+                                uint32_t seq0, uint32_t inflight,
+                                const uint32_t *d_acked, uint32_t *d_sent_ms, uint32_t now_ms,
+                                uint32_t timeout_ms, uint32_t flags,
+                                void *d_wire, size_t wire_stride, uint32_t max_sel,
+                                uint32_t *d_sel, uint32_t *d_wire_len, uint32_t *d_crc_out,
+                                uint32_t *d_counts, void *d_work, size_t work_bytes, void *stream);
+
 /* ---- device-side ACK generation: the receiver's reply ring ---------------------------
    The fourth call of the protocol loop: it follows wtp_accept_data_packets on the same
    stream, takes the same batch (datagrams as in wtp_crc32_verify_batch), seq0 and window,
@@ -487,7 +544,10 @@ int wtp_rx_advance(const void *d_img, const uint32_t *d_slot_len, uint32_t windo
    advance gives the two calls separate buffers.  a = min(*d_adv, slots).  For s < slots
    with t = s + a: d_acked_next[s] = d_acked[t] if t < slots, else 0, and d_sent_ms_next[s] =
    d_sent_ms[t] if t < slots, else fill_ms (any value; the entries behind the shifted ones
-   belong to packets not sent yet).  The inputs and *d_adv are only read; nothing outside
+   belong to packets not sent yet).  With fill_ms = now_ms - timeout_ms - 1 those entries
+   are due at the next wtp_tx_build_retransmit_var, which then also makes a packet's first
+   transmission, in slot order with the retransmits: a sender round over records is ingest
+   -> advance -> that call.  The inputs and *d_adv are only read; nothing outside
    the two output arrays is written.  slots == 0 is valid and launches nothing.  WTP_EINVAL
    (before any device is touched): slots > WTP_TX_MAX_INFLIGHT, a NULL pointer with slots >
    0, an output array overlapping an input array or the other output (arrays that touch
