@@ -1,0 +1,429 @@
+"""What the protocol GPU tests (tests/test_gpu_<call>.py) share: the library fixtures, the
+u32 conversions, guarded device buffers, the first-mismatch reporter, the graph capture and
+replay choreography, the record batch of the mixed-length calls, and the device endpoints
+behind the model loops.  Nothing here is about one call; a new call's test file takes these
+from here and defines none of its own."""
+import numpy as np
+import pytest
+
+import buildvar_model
+import oracle as O
+import retx_model as R
+
+torch = pytest.importorskip("torch")
+DATA_ERROR_BITS = 0b101  # wtp_device_status: bit 0 (length > max), bit 2 (recv_len changed)
+MAXP, STRIDE, M32 = R.MAXP, R.STRIDE, R.M32
+GUARD_WORD = 0x5A5A5A5A
+
+
+def assert_no_data_error(W):
+    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+
+
+# ---- fixtures ---------------------------------------------------------------------------------
+def _library():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import wtp_crc32 as W
+    return W
+
+
+@pytest.fixture(scope="module")
+def W():
+    """The binding after wtp_init(0), with the device status cleared."""
+    W = _library()
+    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
+    W.device_status(0, clear=True)
+    return W
+
+
+@pytest.fixture(scope="module")
+def W_noinit():
+    """The binding with the device status cleared and no wtp_init: for the calls that read
+    no library table, whose tests show that they need none."""
+    W = _library()
+    W.device_status(0, clear=True)
+    return W
+
+
+# ---- conversions ------------------------------------------------------------------------------
+def s32(a):
+    """The int32 view of a host array of uint32 values (torch has no uint32 arithmetic)."""
+    return np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)
+
+
+def dev_s32(a):
+    """s32(a) as a device tensor."""
+    return torch.from_numpy(s32(a)).cuda()
+
+
+def u32(t):
+    """The host uint32 view of an int32 tensor."""
+    return t.cpu().numpy().view(np.uint32)
+
+
+# ---- guarded buffers --------------------------------------------------------------------------
+class Words:
+    """A device array of n u32 (or u64) words behind a view `t`, with 4 guard words
+    (0x5A5A5A5A) after it.  Words(array) or Words(value, n)."""
+
+    def __init__(self, init, n=None, dtype=np.uint32, device="cuda"):
+        self.np_t, self.guard = dtype, dtype(GUARD_WORD)
+        init = np.full(n, init, dtype=dtype) if n is not None else np.ascontiguousarray(init, dtype=dtype)
+        self.n = init.size
+        signed = np.int32 if dtype is np.uint32 else np.int64
+        self.buf = torch.from_numpy(np.concatenate([init, np.full(4, self.guard, dtype)]).view(signed)).to(device)
+        self.t = self.buf[:max(self.n, 1)]
+
+    def get(self):
+        h = self.buf.cpu().numpy().view(self.np_t)
+        assert (h[self.n:] == self.guard).all()  # nothing written past the array
+        return h[:self.n].copy()
+
+
+class Bytes:
+    """`size` payload bytes on the device, `off` bytes past `front` guard bytes at the start of
+    a 16-B aligned allocation, and `back` guard bytes behind them (none with flush: the
+    payload ends with its allocation).  The payload is a copy of `host`, or `fill`; the guards
+    hold `guard`.  `t` is the view from the payload's first byte on."""
+
+    def __init__(self, host=None, fill=None, size=None, off=0, front=0, back=16, guard=0xC3, flush=False, device="cuda"):
+        self.host = None if host is None else np.ascontiguousarray(host, dtype=np.uint8)
+        self.size = size if host is None else self.host.size
+        self.lo, self.guard = front + off, guard
+        self.buf = torch.full((self.lo + self.size + (0 if flush else back),), guard, dtype=torch.uint8, device=device)
+        assert self.buf.data_ptr() % 16 == 0
+        if host is not None:
+            self.payload.copy_(torch.from_numpy(self.host))
+        elif fill != guard:
+            self.payload.fill_(fill)
+        self.t = self.buf[self.lo:]
+
+    @property
+    def payload(self):
+        return self.buf[self.lo:self.lo + self.size]
+
+    def get(self):
+        """The payload on the host, after asserting that both guards are intact."""
+        h = self.buf.cpu().numpy()
+        assert (h[:self.lo] == self.guard).all() and (h[self.lo + self.size:] == self.guard).all()  # nothing outside
+        return h[self.lo:self.lo + self.size]
+
+    def check_guards(self):
+        """The guard asserts alone, on the device: for payloads too large to bring to the host."""
+        assert bool((self.buf[:self.lo] == self.guard).all()) and bool((self.buf[self.lo + self.size:] == self.guard).all())
+
+
+def assert_bytes_equal(got, want, unit, describe):
+    """got == want, or an AssertionError that says how many bytes differ and where the first
+    one is: its `unit`-byte unit (a slot, a ring entry), the byte within it, and the caller's
+    context, `describe` (a string, or a function of the unit's index)."""
+    if np.array_equal(got, want):
+        return
+    bad = np.flatnonzero(got != want)
+    first = int(bad[0])
+    context = describe(first // unit) if callable(describe) else describe
+    raise AssertionError(f"{bad.size} bytes differ, first at {first}: unit {first // unit}, byte {first % unit} ({context})")
+
+
+# ---- graphs -----------------------------------------------------------------------------------
+def capture(call, stream=None):
+    """`call` once on a side stream (outside the capture: what it leaves behind is the state
+    the graph starts from), then captured there.  Returns (graph, stream)."""
+    stream = torch.cuda.Stream() if stream is None else stream
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        call()
+    stream.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        call()
+    return graph, stream
+
+
+def replay_each_then_together(g, alone, others, together):
+    """`g` (an object with graph, stream, reset(*args) and check()) replayed alone once per
+    argument tuple of `alone`, each time reset before and checked after; then `others()` makes
+    two more, h and k, all three are reset with the tuples of `together` and replayed at once,
+    each on its own stream, and checked.  Returns (g, h, k)."""
+    for args in alone:
+        g.reset(*args)
+        torch.cuda.synchronize()
+        g.graph.replay()
+        torch.cuda.synchronize()
+        g.check()
+    h, k = others()
+    for x, args in zip((g, h, k), together):
+        x.reset(*args)
+    torch.cuda.synchronize()
+    for x in (h, k, g):
+        with torch.cuda.stream(x.stream):
+            x.graph.replay()
+    torch.cuda.synchronize()
+    for x in (g, h, k):
+        x.check()
+    return g, h, k
+
+
+# ---- records and rings ------------------------------------------------------------------------
+class Batch:
+    """The device copy of a batch of records: `base` at byte `base_off` of its allocation (16
+    guard bytes after it), offsets (u64) and lengths (u32)."""
+
+    def __init__(self, base, offs, lens, base_off=0, base_bytes=None):
+        self.mem = Bytes(base, off=base_off)
+        self.host = self.mem.host
+        self.offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        self.lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        self.n = self.lens.size
+        self.base_bytes = self.host.size if base_bytes is None else base_bytes
+        self.base = self.mem.t
+        self.o = torch.from_numpy(np.concatenate([self.offs, [np.uint64(0x7E7E)]]).view(np.int64)).cuda()
+        self.l = Words(self.lens)
+
+    def phases(self):
+        """The source address mod 16 of every non-empty payload."""
+        return set(((self.base.data_ptr() + self.offs[self.lens > 0]) % 16).astype(int).tolist())
+
+    def check_untouched(self):
+        assert np.array_equal(self.mem.get(), self.host)
+        assert np.array_equal(self.o.cpu().numpy().view(np.uint64), np.concatenate([self.offs, [np.uint64(0x7E7E)]]))
+        assert np.array_equal(self.l.get(), self.lens)
+
+
+def packed(lens, salt=0, base_off=0):
+    """A Batch of synthetic records of these lengths, back to back."""
+    lens = np.asarray(lens, dtype=np.uint32)
+    return Batch(O.synth_fill_np(max(int(lens.sum()), 1), start_byte=salt), buildvar_model.packed_offsets(lens), lens,
+                 base_off, base_bytes=int(lens.sum()))
+
+
+def datagram_ring(dgrams, stride, salt=0):
+    """(ring, recv_len): `dgrams` in `stride`-byte slots (cut at the slot's end; recv_len
+    keeps the full length); the slot bytes past a datagram are random, so a copy that ran
+    past recv_len would show."""
+    rng = np.random.default_rng(len(dgrams) * 131 + stride + salt)
+    ring = rng.integers(0, 256, len(dgrams) * stride, dtype=np.uint8)
+    rl = np.zeros(len(dgrams), dtype=np.uint32)
+    for i, d in enumerate(dgrams):
+        cut = min(len(d), stride)
+        ring[i * stride:i * stride + cut] = np.frombuffer(d[:cut], dtype=np.uint8)
+        rl[i] = len(d)
+    return ring, rl
+
+
+# ---- device endpoints -------------------------------------------------------------------------
+def _z(k, v=0):
+    return torch.full((k,), v, dtype=torch.int32, device="cuda")
+
+
+class DevEnd:
+    """Both windows on the device, behind the calls of retx_model.transfer: no payload byte
+    crosses to the host (it reads back verdicts, 8 header bytes per datagram and counts).
+    The state is sized by the transfer; rx_state and tx_state give the calls their part of it."""
+
+    def __init__(self, W, src, total, nchunks, window, seq_base):
+        self.W, self.src, self.total, self.window, self.seq_base = W, src, total, window, seq_base
+        self.counts, self.ack = _z(2), _z(1)
+        self.icounts = self.counts  # where ingest_ring leaves its counts
+        self.alloc_state(nchunks, window)
+        self.retx_wire = torch.zeros((0, STRIDE), dtype=torch.uint8, device="cuda")
+        self.retx_len = _z(0)
+
+    def alloc_state(self, nchunks, window):
+        self.acked, self.sent, self.slot_len = _z(nchunks + window), _z(nchunks + window), _z(nchunks + window, -1)
+        self.img = torch.full(((nchunks + window) * MAXP,), 0xA5, dtype=torch.uint8, device="cuda")
+
+    def rx_state(self, rbase):
+        """(img, slot_len) from chunk rbase on."""
+        return self.img[rbase * MAXP:], self.slot_len[rbase:]
+
+    def tx_state(self, sbase):
+        """(acked, sent) from chunk sbase on."""
+        return self.acked[sbase:], self.sent[sbase:]
+
+    def seq(self, chunk):
+        return (self.seq_base + chunk) & M32
+
+    def send(self, c0, cnt, now):
+        wire = torch.zeros((cnt, STRIDE), dtype=torch.uint8, device="cuda")
+        wlen = torch.zeros(cnt, dtype=torch.int32, device="cuda")
+        if cnt:
+            nbytes = min(self.total, (c0 + cnt) * MAXP) - c0 * MAXP
+            self.W.build_data_packets(self.src[c0 * MAXP:], nbytes, self.seq(c0), wire, STRIDE, wlen)
+            self.tx_state(c0)[1][:cnt] = int(s32([now])[0])
+        self.wire, self.wlen = torch.cat([wire, self.retx_wire]), torch.cat([wlen, self.retx_len])
+        return self.wire.shape[0]
+
+    def accept(self, idx, rbase):
+        n = idx.size
+        sel = torch.from_numpy(idx.astype(np.int64)).cuda()
+        ring, rl = self.wire[sel].contiguous(), self.wlen[sel].contiguous()
+        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+        self.W.accept_data_packets(ring if n else ok, STRIDE, rl if n else self.ack, n, self.seq(rbase), self.window,
+                                   *self.rx_state(rbase), ok, None, self.ack)
+        hdr = np.ascontiguousarray(ring[:, :8].cpu().numpy()).reshape(n, 8).view(">u4")
+        return (ok[:n].cpu().numpy(), hdr[:, 0].astype(np.uint32), hdr[:, 1].astype(np.uint32),
+                int(self.ack.cpu().numpy().view(np.uint32)[0]))
+
+    def ingest(self, acks, mode, sbase, inflight):
+        ring, rl = R.make_ring(acks, 16)
+        n = rl.size
+        d = torch.from_numpy(ring).cuda()
+        r = torch.from_numpy(s32(rl)).cuda() if n else self.ack
+        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+        self.W.tx_ingest_acks(d, 16, r, n, mode, self.seq(sbase), inflight, self.tx_state(sbase)[0], ok, None, self.counts)
+        return int(self.counts[0].item())
+
+    def retransmit(self, sbase, inflight, now, timeout, flags, max_sel):
+        wire = torch.zeros((max_sel, STRIDE), dtype=torch.uint8, device="cuda")
+        sel, wlen = (torch.zeros(max_sel, dtype=torch.int32, device="cuda") for _ in range(2))
+        self.W.tx_build_retransmit(self.src[sbase * MAXP:], self.total - sbase * MAXP, self.seq(sbase), inflight,
+                                   *self.tx_state(sbase), now, timeout, flags, wire, STRIDE, max_sel, sel, wlen, self.counts)
+        e = int(self.counts[0].item())
+        self.retx_wire, self.retx_len = wire[:e], wlen[:e]
+        return sel[:e].cpu().numpy()
+
+
+class DevAckEnd(DevEnd):
+    """DevEnd behind the calls of ack_model.transfer.  The ACK ring is built by
+    wtp_rx_build_acks and never leaves the device: the lossy channel is an index_select over
+    its entries, and the selected ring goes straight into wtp_tx_ingest_acks.  The host reads
+    back counts only."""
+
+    def accept(self, idx, rbase):
+        n = self.n = idx.size
+        sel = torch.from_numpy(idx.astype(np.int64)).cuda()
+        self.ring, self.rl = self.wire[sel].contiguous(), self.wlen[sel].contiguous()
+        self.ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+        self.place = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
+        self.W.accept_data_packets(self.ring if n else self.ok, STRIDE, self.rl if n else self.ack, n, self.seq(rbase),
+                                   self.window, *self.rx_state(rbase), self.ok, self.place, self.ack)
+        return int(u32(self.ack)[0])
+
+    def build_acks(self, mode, rbase):
+        n = self.n
+        self.ack_ring = torch.zeros((max(n, 1), 16), dtype=torch.uint8, device="cuda")
+        self.W.rx_build_acks(self.ring if n else self.ok, STRIDE, self.rl if n else self.ack, n, mode, self.seq(rbase),
+                             self.window, self.ok, self.place, self.rx_state(rbase)[1], self.ack_ring, 16, 0, n, None,
+                             self.counts)
+        return int(self.counts[0].item())
+
+    def ingest_ring(self, aidx, mode, sbase, inflight):
+        n = aidx.size
+        ring = self.ack_ring.index_select(0, torch.from_numpy(aidx.astype(np.int64)).cuda())
+        rl = torch.full((max(n, 1),), 16, dtype=torch.int32, device="cuda")
+        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+        self.W.tx_ingest_acks(ring if n else ok, 16, rl, n, mode, self.seq(sbase), inflight, self.tx_state(sbase)[0], ok,
+                              None, self.icounts)
+        return int(self.icounts[0].item())
+
+
+class DevBoundedEnd(DevAckEnd):
+    """DevAckEnd with bounded state: `acked` / `sent` hold `window` entries in two buffers slid
+    by wtp_tx_advance (fed on the device with the count wtp_tx_ingest_acks wrote, kept in its
+    own buffer so that retransmit's counts do not overwrite it), and `slot_len` / `img` hold
+    `window` slots in two buffers slid by wtp_rx_advance (fed with wtp_rx_deliver's counts,
+    which also appends the leading run to the file)."""
+
+    def alloc_state(self, nchunks, window):
+        self.acked, self.sent = [_z(window), _z(window)], [_z(window), _z(window)]
+        self.slot_len = [_z(window, -1), _z(window, -1)]
+        self.img = [torch.full((window * MAXP,), 0xA5, dtype=torch.uint8, device="cuda") for _ in range(2)]
+        self.file = torch.full((self.total + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+        self.adv = self.icounts = _z(2)
+        self.dcounts = torch.zeros(4, dtype=torch.int64, device="cuda")
+        self.work = torch.empty(self.W.rx_deliver_work_bytes(window), dtype=torch.uint8, device="cuda")
+        self.sbase = self.off = 0
+
+    def rx_state(self, rbase):
+        return self.img[0], self.slot_len[0]
+
+    def tx_state(self, sbase):
+        return self.acked[0][sbase - self.sbase:], self.sent[0][sbase - self.sbase:]
+
+    def send(self, c0, cnt, now):
+        if cnt:
+            assert 0 <= c0 - self.sbase and c0 - self.sbase + cnt <= self.window
+        return super().send(c0, cnt, now)
+
+    def accept(self, idx, rbase):
+        ack = super().accept(idx, rbase)
+        self.lead = (ack - self.seq(rbase)) & M32
+        return ack
+
+    def build_acks(self, mode, rbase):
+        emitted = super().build_acks(mode, rbase)
+        # the end of the receiver's round: flush the leading run to the file and slide by it
+        w = self.window
+        self.W.rx_deliver(self.img[0], self.slot_len[0], w, w, self.file, self.total, self.off, None, None, self.dcounts,
+                          work=self.work)
+        self.W.rx_advance(self.img[0], self.slot_len[0], w, self.dcounts, self.img[1], self.slot_len[1])
+        self.img.reverse()
+        self.slot_len.reverse()
+        k, run, pk, _ = self.dcounts.cpu().tolist()
+        assert k == run == self.lead  # deliver's run is accept's cumulative ACK
+        self.off += pk
+        return emitted
+
+    def ingest_ring(self, aidx, mode, sbase, inflight):
+        assert sbase == self.sbase
+        self.advance = super().ingest_ring(aidx, mode, sbase, inflight)
+        return self.advance
+
+    def retransmit(self, sbase, inflight, now, timeout, flags, max_sel):
+        sel = super().retransmit(sbase, inflight, now, timeout, flags, max_sel)
+        # the end of the sender's round: slide by the count ingest left on the device
+        self.W.tx_advance(self.acked[0], self.sent[0], self.window, self.adv, 0, self.acked[1], self.sent[1])
+        self.acked.reverse()
+        self.sent.reverse()
+        self.sbase += self.advance
+        return sel
+
+
+class DevStreamEnd:
+    """The receiver of advance_model.stream_rounds on the device: two (img, slot_len) pairs of
+    `window` slots and nothing sized by the transfer but the output stream.  A round is accept
+    -> rx_build_acks -> rx_deliver -> rx_advance on the stream, the swap of the pairs, and one
+    synchronisation to read deliver's counts."""
+
+    def __init__(self, W, wire, wl, n, stride, seq0, window, total):
+        self.W, self.wire, self.wl, self.n, self.stride, self.seq0, self.window = W, wire, wl, n, stride, seq0, window
+        self.img = [torch.full((window * MAXP,), 0x3C, dtype=torch.uint8, device="cuda") for _ in range(2)]
+        self.sl = [torch.full((window,), -1, dtype=torch.int32, device="cuda") for _ in range(2)]
+        self.whole = Bytes(fill=0xA5, size=total, front=64, back=64, guard=0xA5)
+        self.total = total
+        self.counts = torch.zeros(4, dtype=torch.int64, device="cuda")
+        self.ack_counts = torch.zeros(2, dtype=torch.int32, device="cuda")
+        self.offs_out = torch.zeros(window, dtype=torch.int64, device="cuda")
+        self.lens_out = torch.zeros(window, dtype=torch.int32, device="cuda")
+        self.work = torch.empty(W.rx_deliver_work_bytes(window), dtype=torch.uint8, device="cuda")
+        self.ack_ring = torch.zeros((window, 16), dtype=torch.uint8, device="cuda")
+        self.offs, self.lens, self.acked = [], [], []
+
+    def round(self, idx, base, off, then=None):
+        """`then`: what a sender puts on the stream behind the receiver's calls, before the
+        round's synchronisation."""
+        W, w, n = self.W, self.window, idx.size
+        sel = torch.from_numpy(idx.astype(np.int64)).cuda()
+        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+        ring = self.wire.view(self.n, self.stride)[sel].contiguous().view(-1) if n else ok  # n == 0: any pointer
+        rl = self.wl[sel].contiguous() if n else self.ack_counts
+        seq = (self.seq0 + base) & M32
+        W.accept_data_packets(ring, self.stride, rl, n, seq, w, self.img[0], self.sl[0], ok)
+        W.rx_build_acks(ring, self.stride, rl, n, R.SELECTIVE, seq, w, ok, None, None, self.ack_ring, 16, 0, w, None,
+                        self.ack_counts)
+        W.rx_deliver(self.img[0], self.sl[0], w, w, self.whole.t, self.total, off, self.offs_out, self.lens_out,
+                     self.counts, work=self.work)
+        W.rx_advance(self.img[0], self.sl[0], w, self.counts, self.img[1], self.sl[1])
+        self.img.reverse()
+        self.sl.reverse()
+        if then is not None:
+            then()
+        torch.cuda.synchronize()
+        counts = self.counts.cpu().numpy().view(np.uint64)
+        k = int(counts[0])
+        assert bool(ok[:n].all()) and u32(self.ack_counts).tolist() == [n, n]  # every arrival is intact and answered
+        self.offs += self.offs_out[:k].cpu().numpy().view(np.uint64).tolist()
+        self.lens += u32(self.lens_out[:k]).tolist()
+        return counts

@@ -7,40 +7,18 @@ import pytest
 
 import accept_model as M
 import oracle as O
+from gpu_support import W  # noqa: F401 (fixture)
+from gpu_support import assert_no_data_error, capture, datagram_ring, dev_s32, u32
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DATA_ERROR_BITS = 0b101  # wtp_device_status: bit 0 (length > max), bit 2 (recv_len changed)
 
 
-@pytest.fixture(scope="module")
-def W():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import wtp_crc32 as W
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
-    W.device_status(0, clear=True)
-    return W
-
-
-def _i32(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def _u32(t, n):
-    return t[:n].cpu().numpy().view(np.uint32)
-
-
-def _ring(dgrams, stride):
-    """(ring, stride, recv_len) of `dgrams` (bytes) in `stride`-byte slots; slot bytes past
-    a datagram are random, so a copy that ran past recv_len would show."""
-    rng = np.random.default_rng(len(dgrams) * 131 + stride)
-    ring = rng.integers(0, 256, len(dgrams) * stride, dtype=np.uint8)
-    rl = np.zeros(len(dgrams), dtype=np.uint32)
-    for i, d in enumerate(dgrams):
-        ring[i * stride:i * stride + len(d)] = np.frombuffer(d, dtype=np.uint8)
-        rl[i] = len(d)
+def _slots(dgrams, stride):
+    """(ring, stride, recv_len) of `dgrams` (bytes, none longer than a slot) in `stride`-byte
+    slots: accept()'s arguments."""
+    ring, rl = datagram_ring(dgrams, stride)
     return ring, stride, rl
 
 
@@ -64,7 +42,7 @@ def accept(W, ring, stride, rl, seq0, win, ring_off=0, with_place=True):
     dbuf = torch.zeros(ring.size + ring_off + 16, dtype=torch.uint8, device="cuda")
     d = dbuf[ring_off:ring_off + max(ring.size, 1)]
     d[:ring.size].copy_(torch.from_numpy(ring))
-    r = _i32(rl) if n else torch.zeros(1, dtype=torch.int32, device="cuda")
+    r = dev_s32(rl) if n else torch.zeros(1, dtype=torch.int32, device="cuda")
     ok = torch.full((max(n, 1),), 7, dtype=torch.uint8, device="cuda")
     place = torch.full((max(n, 1),), 12345, dtype=torch.int32, device="cuda")
     ack = torch.full((1,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
@@ -75,14 +53,14 @@ def accept(W, ring, stride, rl, seq0, win, ring_off=0, with_place=True):
                                                                 win.h_slot_len)
     assert np.array_equal(ok[:n].cpu().numpy(), want_ok)
     if with_place:
-        assert np.array_equal(_u32(place, n), want_place)
-    assert np.array_equal(_u32(win.slot_len, win.window), want_sl)
+        assert np.array_equal(u32(place[:n]), want_place)
+    assert np.array_equal(u32(win.slot_len[:win.window]), want_sl)
     got_out = win.out[:win.window * M.MAXP].cpu().numpy()
     assert np.array_equal(got_out, want_out)
-    assert int(_u32(ack, 1)[0]) == want_ack
+    assert int(u32(ack[:1])[0]) == want_ack
     assert (win.buf[win.buf.numel() - 16:] == 0xA5).all()  # nothing written past the image
     assert W.LIB.wtp_last_kernel().decode() == "k_accept_place"
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
     win.h_out, win.h_slot_len = want_out, want_sl
     return want_ok, want_place, want_ack
 
@@ -119,7 +97,7 @@ def test_every_length(W):
     1484 intact but not placed."""
     dg = [O.build_datagram(ln, _payload(ln, ln)) for ln in range(1485)]
     win = Window(1500)
-    ok, place, ack = accept(W, *_ring(dg, 1504), 0, win)
+    ok, place, ack = accept(W, *_slots(dg, 1504), 0, win)
     assert ok.all()
     assert np.array_equal(place[:1457], np.arange(1457)) and (place[1457:] == M.NOT_PLACED).all()
     assert ack == 1457
@@ -137,7 +115,7 @@ def test_corruption(W):
     dg[5][13] ^= 0x04         # checksum
     dg[6][7] ^= 0x01          # seqNum 6 -> 7: arrives before the real 7, so it wins slot 7
     win = Window(8)
-    ok, place, ack = accept(W, *_ring([bytes(d) for d in dg], 1472), 0, win)
+    ok, place, ack = accept(W, *_slots([bytes(d) for d in dg], 1472), 0, win)
     assert ok.tolist() == [1, 1, 0, 1, 1, 0, 1, 1]
     assert place.tolist() == [0, 1, M.NOT_PLACED, 3, 4, M.NOT_PLACED, 7, M.NOT_PLACED]
     assert ack == 2 and win.h_slot_len[2] == M.EMPTY and win.h_slot_len[5] == M.EMPTY and win.h_slot_len[6] == M.EMPTY
@@ -149,14 +127,14 @@ def test_window_edges_and_empty_window(W):
     seq0, window = 1000, 16
     seqs = [seq0 - 1, seq0, seq0 + window - 1, seq0 + window]
     dg = [O.build_datagram(s, _payload(s, 1456 - 16 * k)) for k, s in enumerate(seqs)]
-    ring, _, rl = _ring(dg, 1472)
+    ring, _, rl = _slots(dg, 1472)
     win = Window(window)
     ok, place, ack = accept(W, ring, 1472, rl, seq0, win)
     assert ok.all() and place.tolist() == [M.NOT_PLACED, 0, window - 1, M.NOT_PLACED] and ack == seq0 + 1
     # a window that starts at seq 0: seq 2^32 - 1 lies below it (unsigned distance 2^32 - 1)
     win = Window(window)
     dg = [O.build_datagram(s, _payload(s, 100)) for s in (0xFFFFFFFF, 0, window - 1, window)]
-    _, place, ack = accept(W, *_ring(dg, 1472), 0, win)
+    _, place, ack = accept(W, *_slots(dg, 1472), 0, win)
     assert place.tolist() == [M.NOT_PLACED, 0, window - 1, M.NOT_PLACED] and ack == 1
     # window == 0: nothing placed, ok still written, ack == seq0; d_place NULL is allowed
     for with_place in (True, False):
@@ -165,7 +143,7 @@ def test_window_edges_and_empty_window(W):
         assert ok.all() and (place == M.NOT_PLACED).all() and ack == seq0
     # n == 0: ack from the existing state
     win = Window(4)
-    accept(W, *_ring([O.build_datagram(7, b"abc"), O.build_datagram(8, b"")], 1472), 7, win)
+    accept(W, *_slots([O.build_datagram(7, b"abc"), O.build_datagram(8, b"")], 1472), 7, win)
     ok, place, ack = accept(W, np.zeros(0, np.uint8), 1472, np.zeros(0, np.uint32), 7, win)
     assert ack == 9
 
@@ -175,7 +153,7 @@ def test_non_data_types_runts_and_long_lengths(W):
     dg = [O.build_datagram(k, _payload(k, 200 + k), ptype=t) for k, t in enumerate((0, 1, 3, 7))]
     dg.append(O.build_datagram(4, _payload(4, 300)))          # the one placeable datagram
     dg += [O.build_datagram(5, _payload(5, 64))] * 4            # runts and over-long, below
-    ring, _, rl = _ring(dg, stride)
+    ring, _, rl = _slots(dg, stride)
     rl[5:9] = [0, 15, stride + 1, 5000]
     win = Window(16)
     ok, place, ack = accept(W, ring, stride, rl, 0, win)
@@ -189,7 +167,7 @@ def test_first_wins_no_tearing(W):
     datagram 1's; a later call never changes a filled slot."""
     n, stride = 2048, 1472
     dg = [O.build_datagram(3, _payload(i, 1456)) for i in range(n)]
-    ring, _, rl = _ring(dg, stride)
+    ring, _, rl = _slots(dg, stride)
     win = Window(8)
     ok, place, ack = accept(W, ring, stride, rl, 0, win)
     assert ok.all() and place.tolist() == [3] + [M.NOT_PLACED] * (n - 1) and ack == 0
@@ -214,10 +192,10 @@ def test_two_batch_window(W):
     lens = [1456] * (window - 1) + [333]
     dg = [O.build_datagram((seq0 + s) & M.M32, _payload(s, lens[s])) for s in range(window)]
     win = Window(window)
-    _, _, ack = accept(W, *_ring(dg[0::2], stride), seq0, win)
+    _, _, ack = accept(W, *_slots(dg[0::2], stride), seq0, win)
     assert ack == (seq0 + 1) & M.M32
     resent = [O.build_datagram((seq0 + s) & M.M32, _payload(s + 99, lens[s])) for s in (0, 4, 30)]  # other bytes
-    _, place, ack = accept(W, *_ring(dg[1::2] + resent, stride), seq0, win)
+    _, place, ack = accept(W, *_slots(dg[1::2] + resent, stride), seq0, win)
     assert place.tolist() == list(range(1, window, 2)) + [M.NOT_PLACED] * 3 and ack == (seq0 + window) & M.M32
     want = b"".join(_payload(s, lens[s]) for s in range(window))
     assert win.h_out[:len(want)].tobytes() == want
@@ -235,7 +213,7 @@ def test_alignment(W, stride, ring_off, out_off):
     perm = rng.permutation(n)
     dg = [O.build_datagram(int(s), _payload(int(s), int(lens[s]))) for s in perm]
     win = Window(n, out_off=out_off)
-    ok, place, ack = accept(W, *_ring(dg, stride), 0, win, ring_off=ring_off)
+    ok, place, ack = accept(W, *_slots(dg, stride), 0, win, ring_off=ring_off)
     assert ok.all() and np.array_equal(place, perm.astype(np.uint32)) and ack == n
 
 
@@ -250,11 +228,11 @@ def test_graph_replay(W):
         dg = [bytearray(O.build_datagram(int(s), _payload(int(s) + salt, int(rng.integers(0, 1457))))) for s in seqs]
         for i in range(0, n, 17):
             dg[i][16 + (len(dg[i]) - 16) // 2 if len(dg[i]) > 16 else 12] ^= 0x40
-        ring, _, rl = _ring([bytes(d) for d in dg], stride)
+        ring, _, rl = _slots([bytes(d) for d in dg], stride)
         return ring, rl
 
     ring, rl = batch(0)
-    d, r = torch.from_numpy(ring).cuda(), _i32(rl)
+    d, r = torch.from_numpy(ring).cuda(), dev_s32(rl)
     win = Window(window)
     ok = torch.zeros(n, dtype=torch.uint8, device="cuda")
     place = torch.zeros(n, dtype=torch.int32, device="cuda")
@@ -264,19 +242,12 @@ def test_graph_replay(W):
         win.slot_len.fill_(-1)
         W.accept_data_packets(d, stride, r, n, seq0, window, win.out, win.slot_len, ok, place, ack)
 
-    cs = torch.cuda.Stream()
-    cs.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(cs):
-        call()
-    cs.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=cs):
-        call()
+    g, _ = capture(call)
     for salt in (0, 1000):
         if salt:
             ring, rl = batch(salt)
             d.copy_(torch.from_numpy(ring))
-            r.copy_(_i32(rl))
+            r.copy_(dev_s32(rl))
         win.out.fill_(0xA5)
         ok.fill_(9)
         place.fill_(9)
@@ -285,8 +256,8 @@ def test_graph_replay(W):
         g.replay()
         torch.cuda.synchronize()
         w_ok, w_place, w_out, w_sl, w_ack = M.accept(ring, stride, rl, seq0, window, win.h_out, win.h_slot_len)
-        assert np.array_equal(ok.cpu().numpy(), w_ok) and np.array_equal(_u32(place, n), w_place)
-        assert np.array_equal(_u32(win.slot_len, window), w_sl)
-        assert np.array_equal(win.out.cpu().numpy(), w_out) and int(_u32(ack, 1)[0]) == w_ack
+        assert np.array_equal(ok.cpu().numpy(), w_ok) and np.array_equal(u32(place[:n]), w_place)
+        assert np.array_equal(u32(win.slot_len[:window]), w_sl)
+        assert np.array_equal(win.out.cpu().numpy(), w_out) and int(u32(ack[:1])[0]) == w_ack
         assert 0 < (w_place != M.NOT_PLACED).sum() < n
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)

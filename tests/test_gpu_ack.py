@@ -10,58 +10,25 @@ import accept_model
 import ack_model as A
 import oracle as O
 import retx_model as R
+from gpu_support import W  # noqa: F401 (fixture: wtp_init for accept's verify; the ACK call needs none)
+from gpu_support import Bytes, DevAckEnd, Words, assert_no_data_error, capture, replay_each_then_together, s32, u32
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DATA_ERROR_BITS = 0b101  # wtp_device_status: bit 0 (length > max), bit 2 (recv_len changed)
 MAXP, STRIDE, SENT = A.MAXP, R.STRIDE, 12345
 MODES = [A.SELECTIVE, A.CUMULATIVE]
 
 
-@pytest.fixture(scope="module")
-def W():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import wtp_crc32 as W
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()  # for accept's verify; the ACK call needs none
-    W.device_status(0, clear=True)
-    return W
-
-
-def _s32(a):
-    return np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)
-
-
-def _u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-class Words:
-    """A u32 device array of n words behind a view, with 4 guard words (0x5A5A5A5A) after it."""
-
-    def __init__(self, init, n=None):
-        init = np.full(n, init, dtype=np.uint32) if n is not None else np.ascontiguousarray(init, dtype=np.uint32)
-        self.n = init.size
-        self.buf = torch.from_numpy(_s32(np.concatenate([init, np.full(4, 0x5A5A5A5A, np.uint32)]))).cuda()
-        self.t = self.buf[:max(self.n, 1)]
-
-    def get(self):
-        h = _u32(self.buf)
-        assert (h[self.n:] == 0x5A5A5A5A).all()  # nothing written past the array
-        return h[:self.n].copy()
-
-
-class Batch:
+class AcceptedBatch:
     """A receive ring on the device after wtp_accept_data_packets on a pre-filled window, with
     the host copies the model needs; accept's outputs are compared with accept_model."""
 
     def __init__(self, W, ring, rl, stride, seq0, window, sl0, ring_off=0):
         self.ring, self.rl, self.stride, self.seq0, self.window, self.n = ring, rl, stride, seq0, window, rl.size
         n = self.n
-        self.dbuf = torch.full((ring.size + ring_off + 16,), 0xC3, dtype=torch.uint8, device="cuda")
-        self.dbuf[ring_off:ring_off + ring.size].copy_(torch.from_numpy(ring))
-        self.d = self.dbuf[ring_off:ring_off + max(ring.size, 1)]
+        self.dbuf = Bytes(ring, off=ring_off)  # 16 guard bytes (0xC3) after it
+        self.d = self.dbuf.t
         self.r, self.sl, self.pl = Words(rl), Words(sl0), Words(SENT, n)
         self.okt = torch.full((n + 16,), 7, dtype=torch.uint8, device="cuda")
         self.img = torch.empty(max(window, 1) * MAXP, dtype=torch.uint8, device="cuda")
@@ -103,7 +70,7 @@ def acks(W, b, mode, skip=0, max_acks=None, ack_stride=16, ack_off=0, with_src=T
     assert W.LIB.wtp_last_kernel().decode() == "k_ack_emit"
     seq, idx, (emitted, total) = A.build_acks(b.ring, b.stride, b.rl, mode, b.seq0, b.window, b.place, b.sl_after, ok=b.ok,
                                               skip=skip, max_acks=max_acks, vectorised=vectorised)
-    assert _u32(cbuf).tolist() == [0x77777777] * 2 + [emitted, total] + [0x77777777] * 2
+    assert u32(cbuf).tolist() == [0x77777777] * 2 + [emitted, total] + [0x77777777] * 2
     rows = wire.view(cap, ack_stride).cpu().numpy()
     assert np.array_equal(rows[:emitted, :16], A.ack_bytes(seq))
     assert (rows[emitted:] == 0xA5).all() and (rows[:, 16:] == 0xA5).all()  # past the count / the datagram
@@ -114,8 +81,8 @@ def acks(W, b, mode, skip=0, max_acks=None, ack_stride=16, ack_off=0, with_src=T
     # every input is only read
     assert np.array_equal(b.r.get(), b.rl) and np.array_equal(b.pl.get(), b.place) and np.array_equal(b.sl.get(), b.sl_after)
     okh = b.okt.cpu().numpy()
-    assert np.array_equal(okh[:n], b.ok) and (okh[n:] == 7).all() and (b.dbuf[b.dbuf.numel() - 16:] == 0xC3).all()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert np.array_equal(okh[:n], b.ok) and (okh[n:] == 7).all() and np.array_equal(b.dbuf.get(), b.ring)
+    assert_no_data_error(W)
     return seq, idx, (emitted, total)
 
 
@@ -124,7 +91,7 @@ def _mixed(W, rng, n, seq0, window, stride=STRIDE, ring_off=0):
     dgrams, _ = A.trace(rng, n, seq0, window, sl0, stride)
     ring, _ = R.make_ring([d[:stride] for d in dgrams], stride)
     rl = np.array([len(d) for d in dgrams], dtype=np.uint32)
-    return Batch(W, ring[:n * stride], rl, stride, seq0, window, sl0, ring_off=ring_off)
+    return AcceptedBatch(W, ring[:n * stride], rl, stride, seq0, window, sl0, ring_off=ring_off)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -213,14 +180,14 @@ def _big(W, mode, slots, seq0, window, prefill):
     torch.cuda.synchronize()
     assert bool(okt.all()) and bool((sl[window:] == -1).all())
     hdr = np.ascontiguousarray(ring[:, :8].cpu().numpy()).reshape(-1)
-    seq, idx, (emitted, total) = A.build_acks(hdr, 8, _u32(rl), mode, seq0, window, _u32(place), _u32(sl)[:window],
+    seq, idx, (emitted, total) = A.build_acks(hdr, 8, u32(rl), mode, seq0, window, u32(place), u32(sl)[:window],
                                               ok=okt.cpu().numpy(), vectorised=True)
-    assert emitted == total == n and tuple(_u32(counts)) == (n, n)
+    assert emitted == total == n and tuple(u32(counts)) == (n, n)
     rows = wire.cpu().numpy()
     assert np.array_equal(rows[:n], A.ack_bytes(seq)) and (rows[n:] == 0xA5).all()
-    assert np.array_equal(_u32(src), np.concatenate([idx, [SENT, SENT]]))
-    assert int(seq[-1]) == int(_u32(ack)[0]) if mode == A.CUMULATIVE else True
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert np.array_equal(u32(src), np.concatenate([idx, [SENT, SENT]]))
+    assert int(seq[-1]) == int(u32(ack)[0]) if mode == A.CUMULATIVE else True
+    assert_no_data_error(W)
     return seq
 
 
@@ -310,7 +277,7 @@ def test_more_than_one_block_count_per_lane(W, mode):
     rows = wire.cpu().numpy()
     assert np.array_equal(rows[:emitted], A.ack_bytes(seq)) and (rows[emitted:] == 0xA5).all()
     assert np.array_equal(pl.get(), place) and np.array_equal(slw.get(), sl) and np.array_equal(r.get(), rl)
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
 
 
 def test_graph_replay(W):
@@ -327,19 +294,12 @@ def test_graph_replay(W):
             self.ring, _ = R.make_ring([d[:STRIDE] for d in dgrams], STRIDE)
             self.rl = np.array([len(d) for d in dgrams], dtype=np.uint32)
             z = lambda k, dt=torch.int32: torch.zeros(k, dtype=dt, device="cuda")  # noqa: E731
-            self.d, self.r = torch.from_numpy(self.ring).cuda(), torch.from_numpy(_s32(self.rl)).cuda()
+            self.d, self.r = torch.from_numpy(self.ring).cuda(), torch.from_numpy(s32(self.rl)).cuda()
             self.sl, self.img, self.ok, self.place, self.ack = z(window), z(window * MAXP, torch.uint8), z(n, torch.uint8), z(n), z(1)
             self.wire, self.src, self.counts = z(n * 16, torch.uint8), z(n), z(2)
             self.work = z(W.rx_ack_work_bytes(n, window, mode), torch.uint8)
-            self.stream = torch.cuda.Stream()
             self.reset()
-            self.stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self.stream):
-                self.call()
-            self.stream.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=self.stream):
-                self.call()
+            self.graph, self.stream = capture(self.call)
             ok, place, _, sl, _ = accept_model.accept(self.ring, STRIDE, self.rl, seq0, window, np.zeros(window * MAXP, np.uint8),
                                                       self.sl0)
             self.want = A.build_acks(self.ring, STRIDE, self.rl, mode, seq0, window, place, sl, ok=ok)
@@ -350,7 +310,7 @@ def test_graph_replay(W):
                             n, self.src, self.counts, work=self.work)
 
         def reset(self):
-            self.sl.copy_(torch.from_numpy(_s32(self.sl0)))
+            self.sl.copy_(torch.from_numpy(s32(self.sl0)))
             self.wire.fill_(0xA5)
             self.src.fill_(SENT)
             self.counts.fill_(0x77777777)
@@ -358,98 +318,16 @@ def test_graph_replay(W):
 
         def check(self):
             seq, idx, (emitted, total) = self.want
-            assert tuple(_u32(self.counts)) == (emitted, total) and emitted > 100
+            assert tuple(u32(self.counts)) == (emitted, total) and emitted > 100
             rows = self.wire.view(n, 16).cpu().numpy()
             assert np.array_equal(rows[:emitted], A.ack_bytes(seq)) and (rows[emitted:] == 0xA5).all()
-            assert np.array_equal(_u32(self.src), np.concatenate([idx, np.full(n - emitted, SENT, np.uint32)]))
+            assert np.array_equal(u32(self.src), np.concatenate([idx, np.full(n - emitted, SENT, np.uint32)]))
 
-    g = G(1, A.CUMULATIVE)
-    for _ in range(3):
-        g.reset()
-        torch.cuda.synchronize()
-        g.graph.replay()
-        torch.cuda.synchronize()
-        g.check()
-    h = G(2, A.SELECTIVE)
-    k = G(3, A.CUMULATIVE)
-    for x in (g, h, k):
-        x.reset()
-    torch.cuda.synchronize()
-    for x in (h, k, g):
-        with torch.cuda.stream(x.stream):
-            x.graph.replay()
-    torch.cuda.synchronize()
-    for x in (g, h, k):
-        x.check()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    replay_each_then_together(G(1, A.CUMULATIVE), [()] * 3, lambda: (G(2, A.SELECTIVE), G(3, A.CUMULATIVE)), [()] * 3)
+    assert_no_data_error(W)
 
 
 # ---- end to end on the device -------------------------------------------------------------------
-class DevEnd:
-    """Both windows on the device behind the calls of ack_model.transfer.  The ACK ring is
-    built by wtp_rx_build_acks and never leaves the device: the lossy channel is an
-    index_select over its entries, and the selected ring goes straight into
-    wtp_tx_ingest_acks.  The host reads back counts only."""
-
-    def __init__(self, W, src, total, nchunks, window, seq_base):
-        self.W, self.src, self.total, self.window, self.seq_base = W, src, total, window, seq_base
-        z = lambda k, v=0: torch.full((k,), v, dtype=torch.int32, device="cuda")  # noqa: E731
-        self.acked, self.sent, self.slot_len = z(nchunks + window), z(nchunks + window), z(nchunks + window, -1)
-        self.img = torch.full(((nchunks + window) * MAXP,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.counts, self.ack = z(2), z(1)
-        self.retx_wire = torch.zeros((0, STRIDE), dtype=torch.uint8, device="cuda")
-        self.retx_len = z(0)
-
-    def seq(self, chunk):
-        return (self.seq_base + chunk) & A.M32
-
-    def send(self, c0, cnt, now):
-        wire = torch.zeros((cnt, STRIDE), dtype=torch.uint8, device="cuda")
-        wlen = torch.zeros(cnt, dtype=torch.int32, device="cuda")
-        if cnt:
-            nbytes = min(self.total, (c0 + cnt) * MAXP) - c0 * MAXP
-            self.W.build_data_packets(self.src[c0 * MAXP:], nbytes, self.seq(c0), wire, STRIDE, wlen)
-            self.sent[c0:c0 + cnt] = int(_s32([now])[0])
-        self.wire, self.wlen = torch.cat([wire, self.retx_wire]), torch.cat([wlen, self.retx_len])
-        return self.wire.shape[0]
-
-    def accept(self, idx, rbase):
-        n = self.n = idx.size
-        sel = torch.from_numpy(idx.astype(np.int64)).cuda()
-        self.ring, self.rl = self.wire[sel].contiguous(), self.wlen[sel].contiguous()
-        self.ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
-        self.place = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
-        self.W.accept_data_packets(self.ring if n else self.ok, STRIDE, self.rl if n else self.ack, n, self.seq(rbase),
-                                   self.window, self.img[rbase * MAXP:], self.slot_len[rbase:], self.ok, self.place, self.ack)
-        return int(_u32(self.ack)[0])
-
-    def build_acks(self, mode, rbase):
-        n = self.n
-        self.ack_ring = torch.zeros((max(n, 1), 16), dtype=torch.uint8, device="cuda")
-        self.W.rx_build_acks(self.ring if n else self.ok, STRIDE, self.rl if n else self.ack, n, mode, self.seq(rbase),
-                             self.window, self.ok, self.place, self.slot_len[rbase:], self.ack_ring, 16, 0, n, None, self.counts)
-        return int(self.counts[0].item())
-
-    def ingest_ring(self, aidx, mode, sbase, inflight):
-        n = aidx.size
-        ring = self.ack_ring.index_select(0, torch.from_numpy(aidx.astype(np.int64)).cuda())
-        rl = torch.full((max(n, 1),), 16, dtype=torch.int32, device="cuda")
-        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
-        self.W.tx_ingest_acks(ring if n else ok, 16, rl, n, mode, self.seq(sbase), inflight, self.acked[sbase:], ok, None,
-                              self.counts)
-        return int(self.counts[0].item())
-
-    def retransmit(self, sbase, inflight, now, timeout, flags, max_sel):
-        wire = torch.zeros((max_sel, STRIDE), dtype=torch.uint8, device="cuda")
-        sel, wlen = (torch.zeros(max_sel, dtype=torch.int32, device="cuda") for _ in range(2))
-        self.W.tx_build_retransmit(self.src[sbase * MAXP:], self.total - sbase * MAXP, self.seq(sbase), inflight,
-                                   self.acked[sbase:], self.sent[sbase:], now, timeout, flags, wire, STRIDE, max_sel, sel,
-                                   wlen, self.counts)
-        e = int(self.counts[0].item())
-        self.retx_wire, self.retx_len = wire[:e], wlen[:e]
-        return sel[:e].cpu().numpy()
-
-
 @pytest.mark.parametrize("mode,seq_base", [(A.SELECTIVE, 0), (A.SELECTIVE, 0xFFFFFF80), (A.CUMULATIVE, 0),
                                            (A.CUMULATIVE, 0xFFFFFF80)])
 def test_end_to_end_transfer_with_device_acks(W, mode, seq_base):
@@ -464,11 +342,11 @@ def test_end_to_end_transfer_with_device_acks(W, mode, seq_base):
                                         R.E2E_SEED, R.E2E_LOSS)
     src = torch.empty(total, dtype=torch.uint8, device="cuda")
     W.synth_fill(src, seed=R.E2E_SEED)
-    end = DevEnd(W, src, total, nchunks, window, seq_base)
+    end = DevAckEnd(W, src, total, nchunks, window, seq_base)
     rounds, sets = A.transfer(end, nchunks, window, seq_base, mode, R.E2E_SEED, R.E2E_LOSS)
     assert rounds == want_rounds and sets == want_sets
     assert torch.equal(end.img[:total], src) and bool((end.img[total:nchunks * MAXP] == 0xA5).all())
     crc = torch.zeros(1, dtype=torch.int32, device="cuda")
     W.crc32_buffer(end.img, total, crc)
-    assert int(_u32(crc)[0]) == O.crc32(host)
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert int(u32(crc)[0]) == O.crc32(host)
+    assert_no_data_error(W)

@@ -10,11 +10,13 @@ import ack_model as A
 import advance_model as M
 import oracle as O
 import retx_model as R
+from gpu_support import W_noinit as W  # noqa: F401 (fixture)
+from gpu_support import Bytes, DevBoundedEnd, DevStreamEnd, Words, assert_bytes_equal, assert_no_data_error, capture
+from gpu_support import dev_s32, replay_each_then_together, u32
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DATA_ERROR_BITS = 0b101  # wtp_device_status: bit 0 (length > max), bit 2 (recv_len changed)
 MAXP, EMPTY, SENT, EDGE, PAGE, STRIDE = M.MAXP, M.EMPTY, 12345, 0xC3, 4096, R.STRIDE
 # wtp_advance.hip: a wave of k_rx_advance takes 64 destination slots per round, four of them at
 # a time (one per 16-lane group), a workgroup has four waves, and the capped grid of 2048
@@ -23,59 +25,14 @@ WAVE_SLOTS, STEP_SLOTS, GROUP_SLOTS, PASS_SLOTS = 64, 4, 256, 2048 * 256
 A_VALUES = [0, 1, 63, 64, 65, "w-1", "w", "w+1", 1 << 32, (1 << 64) - 1]
 
 
-@pytest.fixture(scope="module")
-def W():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import wtp_crc32 as W
-    W.device_status(0, clear=True)
-    return W
-
-
-def _s32(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def _u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
 def _a(a, window):
     return {"w-1": window - 1, "w": window, "w+1": window + 1}.get(a, a)
 
 
-class Arr:
-    """A device array of n u32 or u64 words behind a view, with 4 guard words after it."""
-
-    def __init__(self, init, dtype, n=None):
-        self.np_t, self.guard = dtype, dtype(0x5A5A5A5A)
-        init = np.full(n, init, dtype=dtype) if n is not None else np.ascontiguousarray(init, dtype=dtype)
-        self.n = init.size
-        signed = np.int32 if dtype is np.uint32 else np.int64
-        self.buf = torch.from_numpy(np.concatenate([init, np.full(4, self.guard, dtype)]).view(signed)).cuda()
-        self.t = self.buf[:max(self.n, 1)]
-
-    def get(self):
-        h = self.buf.cpu().numpy().view(self.np_t)
-        assert (h[self.n:] == self.guard).all()  # nothing written past the array
-        return h[:self.n].copy()
-
-
-class Img:
+def Img(host, off=0, flush=False):
     """An image of `host` bytes on the device, `off` bytes past a page of sentinel at a 16-B
     aligned address, another page behind it; flush: the image ends with its allocation."""
-
-    def __init__(self, host, off=0, flush=False):
-        self.host, self.lo = np.ascontiguousarray(host, dtype=np.uint8), PAGE + off
-        self.buf = torch.full((self.lo + self.host.size + (0 if flush else PAGE),), EDGE, dtype=torch.uint8, device="cuda")
-        assert self.buf.data_ptr() % 16 == 0
-        self.buf[self.lo:self.lo + self.host.size].copy_(torch.from_numpy(self.host))
-        self.t = self.buf[self.lo:]
-
-    def get(self):
-        h = self.buf.cpu().numpy()
-        assert (h[:self.lo] == EDGE).all() and (h[self.lo + self.host.size:] == EDGE).all()  # the sentinel pages
-        return h[self.lo:self.lo + self.host.size]
+    return Bytes(host, off=off, front=PAGE, back=PAGE, guard=EDGE, flush=flush)
 
 
 def mixed_lens(n, seed=0):
@@ -97,20 +54,16 @@ def run(W, lens, a, salt=0, fill=0x3C, src_off=0, dst_off=0, flush=False, window
     window = lens.size if window is None else window
     src = Img(O.synth_fill_np(max(lens.size, 1) * MAXP, start_byte=salt)[:lens.size * MAXP], src_off, flush)
     dst = Img(np.full(lens.size * MAXP, fill, np.uint8), dst_off, flush)
-    sl, nsl, adv = Arr(lens, np.uint32), Arr(SENT, np.uint32, lens.size), Arr([a], np.uint64)
+    sl, nsl, adv = Words(lens), Words(SENT, lens.size), Words([a], dtype=np.uint64)
     W.rx_advance(src.t, sl.t, window, adv.t, dst.t, nsl.t)
     torch.cuda.synchronize()
     if window:
         assert W.LIB.wtp_last_kernel().decode() == "k_rx_advance"
     want_img, want_sl = M.rx_advance(src.host, lens, window, a, dst.host, np.full(lens.size, SENT, np.uint32))
     assert np.array_equal(nsl.get(), want_sl)
-    got = dst.get()
-    if not np.array_equal(got, want_img):
-        bad = np.flatnonzero(got != want_img)
-        raise AssertionError(f"{bad.size} image bytes differ, first at slot {bad[0] // MAXP} byte {bad[0] % MAXP} "
-                             f"(window {window}, a {a}, offsets {src_off}, {dst_off})")
+    assert_bytes_equal(dst.get(), want_img, MAXP, f"image slots: window {window}, a {a}, offsets {src_off}, {dst_off}")
     assert np.array_equal(src.get(), src.host) and np.array_equal(sl.get(), lens) and adv.get().tolist() == [a]
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
     return want_sl
 
 
@@ -176,12 +129,12 @@ def test_images_and_states_that_touch(W):
     host = O.synth_fill_np(w * MAXP, start_byte=6)
     both = torch.full((2 * w * MAXP,), 0x3C, dtype=torch.uint8, device="cuda")
     both[:w * MAXP].copy_(torch.from_numpy(host))
-    sls = _s32(np.concatenate([lens, np.full(w, SENT, np.uint32)]))
-    adv = Arr([9], np.uint64)
+    sls = dev_s32(np.concatenate([lens, np.full(w, SENT, np.uint32)]))
+    adv = Words([9], dtype=np.uint64)
     W.rx_advance(both, sls, w, adv.t, both[w * MAXP:], sls[w:])
     torch.cuda.synchronize()
     want_img, want_sl = M.rx_advance(host, lens, w, 9, np.full(w * MAXP, 0x3C, np.uint8), np.full(w, SENT, np.uint32))
-    got, gsl = both.cpu().numpy(), _u32(sls)
+    got, gsl = both.cpu().numpy(), u32(sls)
     assert np.array_equal(got[:w * MAXP], host) and np.array_equal(got[w * MAXP:], want_img)
     assert np.array_equal(gsl[:w], lens) and np.array_equal(gsl[w:], want_sl)
 
@@ -194,7 +147,7 @@ def test_state_only_at_the_largest_window(W):
     lens = rng.integers(0, 1 << 32, w, dtype=np.uint64).astype(np.uint32)
     valid = rng.random(w) < 0.3
     lens[valid] = rng.integers(0, MAXP + 1, int(valid.sum()))  # valid lengths too
-    sl, nsl, adv = Arr(lens, np.uint32), Arr(SENT, np.uint32, w), Arr([a], np.uint64)
+    sl, nsl, adv = Words(lens), Words(SENT, w), Words([a], dtype=np.uint64)
     W.rx_advance(None, sl.t, w, adv.t, None, nsl.t)
     torch.cuda.synchronize()
     assert W.LIB.wtp_last_kernel().decode() == "k_rx_advance"
@@ -225,7 +178,7 @@ def big(W, lens, a, fill=0x3C, seed=0xB16):
     before = src.clone()
     dst = torch.full((PAGE + w * MAXP + PAGE,), EDGE, dtype=torch.uint8, device="cuda")
     dst[PAGE:PAGE + w * MAXP] = fill
-    sl, nsl, adv = Arr(lens, np.uint32), Arr(SENT, np.uint32, w), Arr([a], np.uint64)
+    sl, nsl, adv = Words(lens), Words(SENT, w), Words([a], dtype=np.uint64)
     W.rx_advance(src[PAGE:], sl.t, w, adv.t, dst[PAGE:], nsl.t)
     torch.cuda.synchronize()
     want, want_sl = device_expect(src[PAGE:PAGE + w * MAXP], lens, a, w, fill)
@@ -237,7 +190,7 @@ def big(W, lens, a, fill=0x3C, seed=0xB16):
         got, v = rows_d[s].cpu().numpy(), int(want_sl[s])
         v = v if v <= MAXP else 0
         assert np.array_equal(got[:v], rows_s[min(s + a, w - 1)].cpu().numpy()[:v]) and (got[v:] == fill).all(), s
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
 
 
 def test_70000_zipf_slots(W):
@@ -268,15 +221,8 @@ def test_graph_replay(W):
             self.lens = mixed_lens(n, seed=salt)
             self.src = Img(O.synth_fill_np(n * MAXP, start_byte=salt))
             self.dst = Img(np.full(n * MAXP, 0x3C, np.uint8))
-            self.sl, self.nsl, self.adv = Arr(self.lens, np.uint32), Arr(SENT, np.uint32, n), Arr([salt], np.uint64)
-            self.stream = torch.cuda.Stream()
-            self.stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self.stream):
-                self.call()
-            self.stream.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=self.stream):
-                self.call()
+            self.sl, self.nsl, self.adv = Words(self.lens), Words(SENT, n), Words([salt], dtype=np.uint64)
+            self.graph, self.stream = capture(self.call)
 
         def call(self):
             W.rx_advance(self.src.t, self.sl.t, n, self.adv.t, self.dst.t, self.nsl.t)
@@ -293,71 +239,11 @@ def test_graph_replay(W):
             assert np.array_equal(self.src.get(), self.src.host) and np.array_equal(self.sl.get(), self.lens)
             assert self.adv.get().tolist() == [self.a]
 
-    g = G(1)
-    for a in (0, 7, n):
-        g.reset(a)
-        torch.cuda.synchronize()
-        g.graph.replay()
-        torch.cuda.synchronize()
-        g.check()
-    h, k = G(2), G(3)
-    for x, a in ((g, 11), (h, 600), (k, 1499)):
-        x.reset(a)
-    torch.cuda.synchronize()
-    for x in (h, k, g):
-        with torch.cuda.stream(x.stream):
-            x.graph.replay()
-    torch.cuda.synchronize()
-    for x in (g, h, k):
-        x.check()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    replay_each_then_together(G(1), [(0,), (7,), (n,)], lambda: (G(2), G(3)), [(11,), (600,), (1499,)])
+    assert_no_data_error(W)
 
 
 # ---- 9. bounded-window streaming round trip ------------------------------------------------------
-class DevStreamEnd:
-    """The receiver of advance_model.stream_rounds on the device: two (img, slot_len) pairs of
-    `window` slots and nothing sized by the transfer but the output stream.  A round is accept
-    -> rx_build_acks -> rx_deliver -> rx_advance on the stream, the swap of the pairs, and one
-    synchronisation to read deliver's counts."""
-
-    def __init__(self, W, wire, wl, n, stride, seq0, window, total):
-        self.W, self.wire, self.wl, self.n, self.stride, self.seq0, self.window = W, wire, wl, n, stride, seq0, window
-        self.img = [torch.full((window * MAXP,), 0x3C, dtype=torch.uint8, device="cuda") for _ in range(2)]
-        self.sl = [torch.full((window,), -1, dtype=torch.int32, device="cuda") for _ in range(2)]
-        self.whole = torch.full((64 + total + 64,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.total = total
-        self.counts = torch.zeros(4, dtype=torch.int64, device="cuda")
-        self.ack_counts = torch.zeros(2, dtype=torch.int32, device="cuda")
-        self.offs_out = torch.zeros(window, dtype=torch.int64, device="cuda")
-        self.lens_out = torch.zeros(window, dtype=torch.int32, device="cuda")
-        self.work = torch.empty(W.rx_deliver_work_bytes(window), dtype=torch.uint8, device="cuda")
-        self.ack_ring = torch.zeros((window, 16), dtype=torch.uint8, device="cuda")
-        self.offs, self.lens, self.acked = [], [], []
-
-    def round(self, idx, base, off):
-        W, w, n = self.W, self.window, idx.size
-        sel = torch.from_numpy(idx.astype(np.int64)).cuda()
-        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
-        ring = self.wire.view(self.n, self.stride)[sel].contiguous().view(-1) if n else ok  # n == 0: any pointer
-        rl = self.wl[sel].contiguous() if n else self.ack_counts
-        seq = (self.seq0 + base) & M.M32
-        W.accept_data_packets(ring, self.stride, rl, n, seq, w, self.img[0], self.sl[0], ok)
-        W.rx_build_acks(ring, self.stride, rl, n, A.SELECTIVE, seq, w, ok, None, None, self.ack_ring, 16, 0, w, None,
-                        self.ack_counts)
-        W.rx_deliver(self.img[0], self.sl[0], w, w, self.whole[64:], self.total, off, self.offs_out, self.lens_out,
-                     self.counts, work=self.work)
-        W.rx_advance(self.img[0], self.sl[0], w, self.counts, self.img[1], self.sl[1])
-        self.img.reverse()
-        self.sl.reverse()
-        torch.cuda.synchronize()
-        counts = self.counts.cpu().numpy().view(np.uint64)
-        k = int(counts[0])
-        assert bool(ok[:n].all()) and _u32(self.ack_counts).tolist() == [n, n]  # every arrival is intact and answered
-        self.offs += self.offs_out[:k].cpu().numpy().view(np.uint64).tolist()
-        self.lens += _u32(self.lens_out[:k]).tolist()
-        return counts
-
-
 def test_bounded_window_streaming_round_trip(W):
     """2000 packed Zipf records whose sequence numbers wrap, through 5 % loss and a receiver of
     two 256-slot window states: the delivered stream, offsets and lengths are the sender's,
@@ -375,20 +261,19 @@ def test_bounded_window_streaming_round_trip(W):
     want = M.stream_rounds(M.ModelStreamEnd(m_wire, m_wl, stride, seq0, window, total))
     # the device loop: the builder gives them
     wire = torch.full((n * stride,), 0xA5, dtype=torch.uint8, device="cuda")
-    wl = _s32(np.zeros(n))
-    W.build_data_packets_var(torch.from_numpy(host).cuda(), total, torch.from_numpy(offs.view(np.int64)).cuda(), _s32(lens),
-                             n, seq0, wire, stride, wl, None)
+    wl = dev_s32(np.zeros(n))
+    W.build_data_packets_var(torch.from_numpy(host).cuda(), total, torch.from_numpy(offs.view(np.int64)).cuda(),
+                             dev_s32(lens), n, seq0, wire, stride, wl, None)
     end = DevStreamEnd(W, wire, wl, n, stride, seq0, window, total)
     got = M.stream_rounds(end)
     assert got == want and len(got) <= M.STREAM_MAX_ROUNDS
-    whole = end.whole.cpu().numpy()
-    assert np.array_equal(whole[64:64 + total], host) and (whole[:64] == 0xA5).all() and (whole[64 + total:] == 0xA5).all()
+    assert np.array_equal(end.whole.get(), host)  # between 64 guard bytes of 0xA5 on both sides
     assert np.array_equal(np.array(end.offs, np.uint64), offs) and np.array_equal(np.array(end.lens, np.uint32), lens)
     crc = torch.zeros(1, dtype=torch.int32, device="cuda")
-    W.crc32_buffer(end.whole[64:], total, crc)
-    assert int(_u32(crc)[0]) == O.crc32(host)
+    W.crc32_buffer(end.whole.t, total, crc)
+    assert int(u32(crc)[0]) == O.crc32(host)
     assert all(t.numel() == window * MAXP for t in end.img) and all(t.numel() == window for t in end.sl)
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
 
 
 # ---- 10. the sender's slide ------------------------------------------------------------------------
@@ -398,10 +283,10 @@ def test_tx_advance(W, slots):
     rng = np.random.default_rng(slots)
     acked = (rng.random(slots) < 0.6).astype(np.uint32) * rng.integers(1, 3, slots).astype(np.uint32)
     sent = rng.integers(0, 1 << 32, slots, dtype=np.uint64).astype(np.uint32)
-    da, ds = Arr(acked, np.uint32), Arr(sent, np.uint32)
+    da, ds = Words(acked), Words(sent)
     fill = 0xFFFFFFF3  # a clock about to wrap
     for a in sorted(set(min(_a(x, slots), M.M32) for x in A_VALUES)):
-        na, ns, adv = Arr(SENT, np.uint32, slots), Arr(SENT, np.uint32, slots), Arr([a], np.uint32)
+        na, ns, adv = Words(SENT, slots), Words(SENT, slots), Words([a])
         W.tx_advance(da.t, ds.t, slots, adv.t, fill, na.t, ns.t)
         torch.cuda.synchronize()
         assert W.LIB.wtp_last_kernel().decode() == "k_tx_advance"
@@ -410,95 +295,6 @@ def test_tx_advance(W, slots):
         assert np.array_equal(na.get(), want_a) and np.array_equal(ns.get(), want_s), (slots, a)
         assert np.array_equal(da.get(), acked) and np.array_equal(ds.get(), sent) and adv.get().tolist() == [a]
     assert W.LIB.wtp_tx_advance(None, None, 0, None, 0, None, None, None) == 0  # no slots: nothing launched
-
-
-class DevEnd:
-    """Both windows on the device behind the calls of ack_model.transfer, as in
-    tests/test_gpu_ack.py, but with bounded state: `acked` / `sent` hold `window` entries in
-    two buffers slid by wtp_tx_advance (fed on the device with the count wtp_tx_ingest_acks
-    wrote, kept in its own buffer so that retransmit's counts do not overwrite it), and
-    `slot_len` / `img` hold `window` slots in two buffers slid by wtp_rx_advance (fed with
-    wtp_rx_deliver's counts, which also appends the leading run to the file)."""
-
-    def __init__(self, W, src, total, nchunks, window, seq_base):
-        self.W, self.src, self.total, self.window, self.seq_base = W, src, total, window, seq_base
-        z = lambda k, v=0: torch.full((k,), v, dtype=torch.int32, device="cuda")  # noqa: E731
-        self.acked, self.sent = [z(window), z(window)], [z(window), z(window)]
-        self.slot_len = [z(window, -1), z(window, -1)]
-        self.img = [torch.full((window * MAXP,), 0xA5, dtype=torch.uint8, device="cuda") for _ in range(2)]
-        self.file = torch.full((total + 64,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.counts, self.adv, self.ack = z(2), z(2), z(1)
-        self.dcounts = torch.zeros(4, dtype=torch.int64, device="cuda")
-        self.work = torch.empty(W.rx_deliver_work_bytes(window), dtype=torch.uint8, device="cuda")
-        self.retx_wire = torch.zeros((0, STRIDE), dtype=torch.uint8, device="cuda")
-        self.retx_len = z(0)
-        self.sbase = self.off = 0
-
-    def seq(self, chunk):
-        return (self.seq_base + chunk) & A.M32
-
-    def send(self, c0, cnt, now):
-        wire = torch.zeros((cnt, STRIDE), dtype=torch.uint8, device="cuda")
-        wlen = torch.zeros(cnt, dtype=torch.int32, device="cuda")
-        if cnt:
-            nbytes = min(self.total, (c0 + cnt) * MAXP) - c0 * MAXP
-            self.W.build_data_packets(self.src[c0 * MAXP:], nbytes, self.seq(c0), wire, STRIDE, wlen)
-            assert 0 <= c0 - self.sbase and c0 - self.sbase + cnt <= self.window
-            self.sent[0][c0 - self.sbase:c0 - self.sbase + cnt] = int(np.array([now], np.uint32).view(np.int32)[0])
-        self.wire, self.wlen = torch.cat([wire, self.retx_wire]), torch.cat([wlen, self.retx_len])
-        return self.wire.shape[0]
-
-    def accept(self, idx, rbase):
-        n = self.n = idx.size
-        sel = torch.from_numpy(idx.astype(np.int64)).cuda()
-        self.ring, self.rl = self.wire[sel].contiguous(), self.wlen[sel].contiguous()
-        self.ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
-        self.place = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
-        self.W.accept_data_packets(self.ring if n else self.ok, STRIDE, self.rl if n else self.ack, n, self.seq(rbase),
-                                   self.window, self.img[0], self.slot_len[0], self.ok, self.place, self.ack)
-        self.lead = (int(_u32(self.ack)[0]) - self.seq(rbase)) & A.M32
-        return int(_u32(self.ack)[0])
-
-    def build_acks(self, mode, rbase):
-        n, w = self.n, self.window
-        self.ack_ring = torch.zeros((max(n, 1), 16), dtype=torch.uint8, device="cuda")
-        self.W.rx_build_acks(self.ring if n else self.ok, STRIDE, self.rl if n else self.ack, n, mode, self.seq(rbase), w,
-                             self.ok, self.place, self.slot_len[0], self.ack_ring, 16, 0, n, None, self.counts)
-        # the end of the receiver's round: flush the leading run to the file and slide by it
-        self.W.rx_deliver(self.img[0], self.slot_len[0], w, w, self.file, self.total, self.off, None, None, self.dcounts,
-                          work=self.work)
-        self.W.rx_advance(self.img[0], self.slot_len[0], w, self.dcounts, self.img[1], self.slot_len[1])
-        self.img.reverse()
-        self.slot_len.reverse()
-        k, run, pk, _ = self.dcounts.cpu().tolist()
-        assert k == run == self.lead  # deliver's run is accept's cumulative ACK
-        self.off += pk
-        return int(self.counts[0].item())
-
-    def ingest_ring(self, aidx, mode, sbase, inflight):
-        assert sbase == self.sbase
-        n = aidx.size
-        ring = self.ack_ring.index_select(0, torch.from_numpy(aidx.astype(np.int64)).cuda())
-        rl = torch.full((max(n, 1),), 16, dtype=torch.int32, device="cuda")
-        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
-        self.W.tx_ingest_acks(ring if n else ok, 16, rl, n, mode, self.seq(sbase), inflight, self.acked[0], ok, None, self.adv)
-        self.advance = int(self.adv[0].item())
-        return self.advance
-
-    def retransmit(self, sbase, inflight, now, timeout, flags, max_sel):
-        wire = torch.zeros((max_sel, STRIDE), dtype=torch.uint8, device="cuda")
-        sel, wlen = (torch.zeros(max_sel, dtype=torch.int32, device="cuda") for _ in range(2))
-        self.W.tx_build_retransmit(self.src[sbase * MAXP:], self.total - sbase * MAXP, self.seq(sbase), inflight,
-                                   self.acked[0], self.sent[0], now, timeout, flags, wire, STRIDE, max_sel, sel, wlen,
-                                   self.counts)
-        # the end of the sender's round: slide by the count ingest left on the device
-        self.W.tx_advance(self.acked[0], self.sent[0], self.window, self.adv, 0, self.acked[1], self.sent[1])
-        self.acked.reverse()
-        self.sent.reverse()
-        self.sbase += self.advance
-        e = int(self.counts[0].item())
-        self.retx_wire, self.retx_len = wire[:e], wlen[:e]
-        return sel[:e].cpu().numpy()
 
 
 @pytest.mark.parametrize("mode,seq_base", [(A.SELECTIVE, 0), (A.SELECTIVE, 0xFFFFFF80), (A.CUMULATIVE, 0),
@@ -515,12 +311,12 @@ def test_end_to_end_transfer_in_two_windows_of_state(W, mode, seq_base):
                                         R.E2E_SEED, R.E2E_LOSS)
     src = torch.empty(total, dtype=torch.uint8, device="cuda")
     W.synth_fill(src, seed=R.E2E_SEED)
-    end = DevEnd(W, src, total, nchunks, window, seq_base)
+    end = DevBoundedEnd(W, src, total, nchunks, window, seq_base)
     rounds, sets = A.transfer(end, nchunks, window, seq_base, mode, R.E2E_SEED, R.E2E_LOSS)
     assert rounds == want_rounds and sets == want_sets
     assert end.off == total and torch.equal(end.file[:total], src) and bool((end.file[total:] == 0xA5).all())
     assert all(t.numel() == window for t in end.acked + end.sent + end.slot_len)
     crc = torch.zeros(1, dtype=torch.int32, device="cuda")
     W.crc32_buffer(end.file, total, crc)
-    assert int(_u32(crc)[0]) == O.crc32(host)
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert int(u32(crc)[0]) == O.crc32(host)
+    assert_no_data_error(W)

@@ -8,71 +8,15 @@ import pytest
 
 import buildvar_model as M
 import oracle as O
+from gpu_support import W_noinit as W  # noqa: F401 (fixture)
+from gpu_support import Batch, Bytes, Words, assert_bytes_equal, assert_no_data_error, capture, packed
+from gpu_support import replay_each_then_together, u32
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DATA_ERROR_BITS = 0b101  # wtp_device_status: bit 0 (length > max), bit 2 (recv_len changed)
 MAXP, SENT, WSENT, GUARD = M.MAXP, 12345, 0xA5, 64
 GROUPS = 2048 * 256  # above the 1280 x 256 datagrams the capped grid takes in one pass (wtp_buildvar.hip)
-
-
-@pytest.fixture(scope="module")
-def W():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import wtp_crc32 as W
-    W.device_status(0, clear=True)
-    return W
-
-
-def _s32(a):
-    return np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)
-
-
-class Words:
-    """A u32 device array of n words behind a view, with 4 guard words (0x5A5A5A5A) after it."""
-
-    def __init__(self, init, n=None):
-        init = np.full(n, init, dtype=np.uint32) if n is not None else np.ascontiguousarray(init, dtype=np.uint32)
-        self.n = init.size
-        self.buf = torch.from_numpy(_s32(np.concatenate([init, np.full(4, 0x5A5A5A5A, np.uint32)]))).cuda()
-        self.t = self.buf[:max(self.n, 1)]
-
-    def get(self):
-        h = self.buf.cpu().numpy().view(np.uint32)
-        assert (h[self.n:] == 0x5A5A5A5A).all()  # nothing written past the array
-        return h[:self.n].copy()
-
-
-class Batch:
-    """The device copy of a batch: `base` at byte `base_off` of its allocation (16 guard
-    bytes after it), offsets (u64) and lengths (u32)."""
-
-    def __init__(self, base, offs, lens, base_off=0, base_bytes=None):
-        self.host = np.ascontiguousarray(base, dtype=np.uint8)
-        self.offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        self.lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        self.n = self.lens.size
-        self.base_bytes = self.host.size if base_bytes is None else base_bytes
-        self.base_off = base_off
-        self.buf = torch.full((self.host.size + base_off + 16,), 0xC3, dtype=torch.uint8, device="cuda")
-        assert self.buf.data_ptr() % 16 == 0
-        self.buf[base_off:base_off + self.host.size].copy_(torch.from_numpy(self.host))
-        self.base = self.buf[base_off:]
-        self.o = torch.from_numpy(np.concatenate([self.offs, [np.uint64(0x7E7E)]]).view(np.int64)).cuda()
-        self.l = Words(self.lens)
-
-    def phases(self):
-        """The source address mod 16 of every non-empty payload."""
-        return set(((self.base.data_ptr() + self.offs[self.lens > 0]) % 16).astype(int).tolist())
-
-    def check_untouched(self):
-        h = self.buf.cpu().numpy()
-        assert np.array_equal(h[self.base_off:self.base_off + self.host.size], self.host)
-        assert (h[:self.base_off] == 0xC3).all() and (h[self.base_off + self.host.size:] == 0xC3).all()
-        assert np.array_equal(self.o.cpu().numpy().view(np.uint64), np.concatenate([self.offs, [np.uint64(0x7E7E)]]))
-        assert np.array_equal(self.l.get(), self.lens)
 
 
 def run(W, b, seq0=0, stride=1472, ring_off=0, with_len=True, with_crc=True):
@@ -80,35 +24,22 @@ def run(W, b, seq0=0, stride=1472, ring_off=0, with_len=True, with_crc=True):
     `ring_off` past a 16-B aligned address; asserts every output and every untouched byte
     against the model; returns the model's (wire, wire_len, crc)."""
     n = b.n
-    whole = torch.full((GUARD + ring_off + n * stride + GUARD,), WSENT, dtype=torch.uint8, device="cuda")
-    assert whole.data_ptr() % 16 == 0
-    wire = whole[GUARD + ring_off:]
+    wire = Bytes(fill=WSENT, size=n * stride, off=ring_off, front=GUARD, back=GUARD, guard=WSENT)
     wl, crc = Words(SENT, n), Words(SENT, n)
-    W.build_data_packets_var(b.base, b.base_bytes, b.o, b.l.t, n, seq0, wire, stride, wl.t if with_len else None,
+    W.build_data_packets_var(b.base, b.base_bytes, b.o, b.l.t, n, seq0, wire.t, stride, wl.t if with_len else None,
                              crc.t if with_crc else None)
     torch.cuda.synchronize()
     if n:
         assert W.LIB.wtp_last_kernel().decode() == "k_build_var"
     want_wire, want_wl, want_crc = M.build(b.host, b.base_bytes, b.offs, b.lens, seq0,
                                            np.full(n * stride, WSENT, dtype=np.uint8), stride)
-    got = whole.cpu().numpy()
-    lo = GUARD + ring_off
-    assert (got[:lo] == WSENT).all() and (got[lo + n * stride:] == WSENT).all()  # nothing outside the ring
-    if not np.array_equal(got[lo:lo + n * stride], want_wire):
-        bad = np.flatnonzero(got[lo:lo + n * stride] != want_wire)
-        raise AssertionError(f"{bad.size} wire bytes differ, first in slot {bad[0] // stride} at byte {bad[0] % stride} "
-                             f"(len {b.lens[bad[0] // stride]}, offset {b.offs[bad[0] // stride]})")
+    got = wire.get()  # nothing outside the ring
+    assert_bytes_equal(got, want_wire, stride, lambda slot: f"wire slots: len {b.lens[slot]}, offset {b.offs[slot]}")
     assert np.array_equal(wl.get(), want_wl if with_len else np.full(n, SENT, np.uint32))
     assert np.array_equal(crc.get(), want_crc if with_crc else np.full(n, SENT, np.uint32))
     b.check_untouched()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
     return want_wire, want_wl, want_crc
-
-
-def packed(lens, salt=0, base_off=0):
-    lens = np.asarray(lens, dtype=np.uint32)
-    return Batch(O.synth_fill_np(max(int(lens.sum()), 1), start_byte=salt), M.packed_offsets(lens), lens, base_off,
-                 base_bytes=int(lens.sum()))
 
 
 # ---- every length, every alignment -----------------------------------------------------------
@@ -230,17 +161,17 @@ def test_more_datagrams_than_the_capped_grid_takes_in_one_round(W):
                                     np.full(600 * 24, WSENT, np.uint8), 24)
         assert np.array_equal(want.reshape(600, 24), head[part]) and np.array_equal(want_crc, crc[part])
     b = Batch(base, offs, lens)
-    whole = torch.full((GUARD + n * stride + GUARD,), WSENT, dtype=torch.uint8, device="cuda")
+    whole = Bytes(fill=WSENT, size=n * stride, front=GUARD, back=GUARD, guard=WSENT)
     wl, out = Words(SENT, n), Words(SENT, n)
-    W.build_data_packets_var(b.base, b.base_bytes, b.o, b.l.t, n, seq0, whole[GUARD:], stride, wl.t, out.t)
+    W.build_data_packets_var(b.base, b.base_bytes, b.o, b.l.t, n, seq0, whole.t, stride, wl.t, out.t)
     torch.cuda.synchronize()
-    slots = whole[GUARD:GUARD + n * stride].view(n, stride)
+    slots = whole.payload.view(n, stride)
     assert torch.equal(slots[:, :24], torch.from_numpy(head).cuda())
     assert bool((slots[:, 24:] == WSENT).all())
-    assert bool((whole[:GUARD] == WSENT).all()) and bool((whole[GUARD + n * stride:] == WSENT).all())
+    whole.check_guards()
     assert np.array_equal(wl.get(), lens + 16) and np.array_equal(out.get(), crc)
     b.check_untouched()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
 
 
 # ---- optional pointers ---------------------------------------------------------------------------
@@ -266,18 +197,16 @@ def test_offsets_above_4_gib(W):
     offs = np.array([top - 3000, top - 1456, top - 700, top - 1, top, top + 1, top + 5003, top + tail - 100], dtype=np.uint64)
     lens = np.array([1456, 1456, 1456, 5, 1456, 333, 17, 100], dtype=np.uint32)
     n, stride = 8, 1472
-    whole = torch.full((GUARD + n * stride + GUARD,), WSENT, dtype=torch.uint8, device="cuda")
+    whole = Bytes(fill=WSENT, size=n * stride, front=GUARD, back=GUARD, guard=WSENT)
     wl, crc, dl = Words(SENT, n), Words(SENT, n), Words(lens)
     do = torch.from_numpy(offs.view(np.int64)).cuda()
-    W.build_data_packets_var(big, top + tail, do, dl.t, n, 0xFFFFFFFC, whole[GUARD:], stride, wl.t, crc.t)
+    W.build_data_packets_var(big, top + tail, do, dl.t, n, 0xFFFFFFFC, whole.t, stride, wl.t, crc.t)
     torch.cuda.synchronize()
     want, want_wl, want_crc = M.build(host, win + tail, offs - np.uint64(top - win), lens, 0xFFFFFFFC,
                                       np.full(n * stride, WSENT, np.uint8), stride)
-    got = whole.cpu().numpy()
-    assert np.array_equal(got[GUARD:GUARD + n * stride], want)
-    assert (got[:GUARD] == WSENT).all() and (got[GUARD + n * stride:] == WSENT).all()
+    assert np.array_equal(whole.get(), want)
     assert np.array_equal(wl.get(), want_wl) and np.array_equal(crc.get(), want_crc) and (want_wl == lens + 16).all()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
 
 
 # ---- graphs ---------------------------------------------------------------------------------------
@@ -295,15 +224,8 @@ def test_graph_replay(W):
             self.seq0 = 0xFFFFFF00 + salt
             self.wire = torch.empty(n * stride, dtype=torch.uint8, device="cuda")
             self.wl, self.crc = Words(SENT, n), Words(SENT, n)
-            self.stream = torch.cuda.Stream()
             self.reset()
-            self.stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self.stream):
-                self.call()
-            self.stream.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=self.stream):
-                self.call()
+            self.graph, self.stream = capture(self.call)
             self.want = M.build(self.b.host, self.b.base_bytes, self.b.offs, self.b.lens, self.seq0,
                                 np.full(n * stride, WSENT, np.uint8), stride)
 
@@ -320,24 +242,8 @@ def test_graph_replay(W):
             assert np.array_equal(self.wire.cpu().numpy(), self.want[0])
             assert np.array_equal(self.wl.get(), self.want[1]) and np.array_equal(self.crc.get(), self.want[2])
 
-    g = G(1)
-    for _ in range(3):
-        g.reset()
-        torch.cuda.synchronize()
-        g.graph.replay()
-        torch.cuda.synchronize()
-        g.check()
-    h, k = G(2), G(3)
-    for x in (g, h, k):
-        x.reset()
-    torch.cuda.synchronize()
-    for x in (h, k, g):
-        with torch.cuda.stream(x.stream):
-            x.graph.replay()
-    torch.cuda.synchronize()
-    for x in (g, h, k):
-        x.check()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    replay_each_then_together(G(1), [()] * 3, lambda: (G(2), G(3)), [()] * 3)
+    assert_no_data_error(W)
 
 
 # ---- round trip --------------------------------------------------------------------------------------
@@ -361,14 +267,14 @@ def test_round_trip_through_accept_and_concat(W):
     W.crc32_concat(crc.t, b.l.t, n, out)
     torch.cuda.synchronize()
     assert bool((ok == 1).all())
-    assert np.array_equal(sl.cpu().numpy().view(np.uint32), lens)
-    assert int(ack.cpu().numpy().view(np.uint32)[0]) == (seq0 + n) & M.M32
+    assert np.array_equal(u32(sl), lens)
+    assert int(u32(ack)[0]) == (seq0 + n) & M.M32
     rows = img.cpu().numpy().reshape(n, MAXP)
     col = np.arange(MAXP)[None, :]
     want = np.full((n, MAXP), 0x3C, dtype=np.uint8)
     mask = col < lens[:, None]
     want[mask] = b.host[:int(lens.sum())]  # packed payloads, row by row
     assert np.array_equal(rows, want)
-    assert int(out.cpu().numpy().view(np.uint32)[0]) == O.crc32(b.host[:int(lens.sum())])
+    assert int(u32(out)[0]) == O.crc32(b.host[:int(lens.sum())])
     assert np.array_equal(wl.get(), lens + 16)
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)

@@ -10,6 +10,7 @@ import pytest
 
 import concat_model as M
 import oracle as O
+from gpu_support import capture, dev_s32, u32
 from test_concat_model import GOLD, binaries, check_digest, digest_transfer  # noqa: F401 (binaries: fixture)
 
 pytestmark = pytest.mark.gpu
@@ -38,14 +39,6 @@ def W():
     return W
 
 
-def _dev_u32(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def _host_u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
 def _words(n, seed):
     return np.random.default_rng(seed).integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
 
@@ -54,11 +47,11 @@ class Out:
     """One result word between two sentinels."""
 
     def __init__(self):
-        self.t = _dev_u32([SENT[0], 0x77777777, SENT[1]])
+        self.t = dev_s32([SENT[0], 0x77777777, SENT[1]])
         self.ptr = self.t[1:2]
 
     def value(self):
-        h = _host_u32(self.t)
+        h = u32(self.t)
         assert (int(h[0]), int(h[2])) == SENT, "a word beside d_out was written"
         return int(h[1])
 
@@ -83,7 +76,7 @@ def buffer(W, view, nbytes, fill=0xFF):
 @pytest.mark.parametrize("n", NS)
 def test_concat_fixed(W, n):
     crc = _words(n, 1000 + n)
-    d = _dev_u32(crc) if n else None
+    d = dev_s32(crc) if n else None
     for length in FIXED_LENS:
         for last in sorted({0, 1, length}):
             got = concat(W, d, None, n, length, last)
@@ -91,14 +84,14 @@ def test_concat_fixed(W, n):
             if n:
                 assert W.LIB.wtp_last_kernel().decode() == "k_concat_fold"
     if n:
-        assert np.array_equal(_host_u32(d), crc)  # d_crc is only read
+        assert np.array_equal(u32(d), crc)  # d_crc is only read
 
 
 @pytest.mark.parametrize("n", [ALL_GROUPS + 1, ALL_GROUPS + 2, ALL_GROUPS + 12_345])
 def test_concat_fixed_all_groups(W, n):
     """The last n of 16-element runs over 1024 workgroups, the first of 17, and a larger one."""
     crc = _words(n, n)
-    assert concat(W, _dev_u32(crc), None, n, 1456, 777) == M.concat_fixed(crc, 1456, 777)
+    assert concat(W, dev_s32(crc), None, n, 1456, 777) == M.concat_fixed(crc, 1456, 777)
 
 
 # ---- concat, variable lengths ----------------------------------------------------------
@@ -114,9 +107,9 @@ def _var_lens(n, seed):
 def test_concat_var(W, n):
     crc, lens = _words(n, 2000 + n), _var_lens(n, 3000 + n)
     if n == 0:
-        assert concat(W, None, _dev_u32([0]), 0) == 0
+        assert concat(W, None, dev_s32([0]), 0) == 0
         return
-    d_crc, d_len = _dev_u32(crc), _dev_u32(lens)
+    d_crc, d_len = dev_s32(crc), dev_s32(lens)
     want = M.concat_var(crc, lens)
     assert concat(W, d_crc, d_len, n) == want
     assert W.LIB.wtp_last_kernel().decode() == "k_concat_var"
@@ -124,12 +117,12 @@ def test_concat_var(W, n):
     # order matters: the reversed input gives the model's value for the reversed input
     rc, rl = crc[::-1].copy(), lens[::-1].copy()
     rwant = M.concat_var(rc, rl)
-    assert concat(W, _dev_u32(rc), _dev_u32(rl), n) == rwant
+    assert concat(W, dev_s32(rc), dev_s32(rl), n) == rwant
     if n >= 63:
         assert rwant != want
     # all lengths zero: the XOR of the CRCs
-    assert concat(W, d_crc, _dev_u32(np.zeros(n, np.uint32)), n) == int(np.bitwise_xor.reduce(crc))
-    assert np.array_equal(_host_u32(d_crc), crc) and np.array_equal(_host_u32(d_len), lens)
+    assert concat(W, d_crc, dev_s32(np.zeros(n, np.uint32)), n) == int(np.bitwise_xor.reduce(crc))
+    assert np.array_equal(u32(d_crc), crc) and np.array_equal(u32(d_len), lens)
 
 
 def test_concat_var_all_groups(W):
@@ -147,13 +140,13 @@ def test_concat_var_all_groups(W):
         want = M.combine(want, int(crc[k]), special[k])
         a = k + 1
     assert a == n
-    assert concat(W, _dev_u32(crc), _dev_u32(lens), n) == want
+    assert concat(W, dev_s32(crc), dev_s32(lens), n) == want
 
 
 def test_concat_fixed_work_independent(W):
     n = 20_000
     crc = _words(n, 5)
-    d = _dev_u32(crc)
+    d = dev_s32(crc)
     want = M.concat_fixed(crc, 1456, 99)
     assert concat(W, d, None, n, 1456, 99, fill=0xFF) == want
     assert concat(W, d, None, n, 1456, 99, fill=0x00) == want
@@ -161,7 +154,7 @@ def test_concat_fixed_work_independent(W):
 
 def test_bad_arguments(W):
     n = 100
-    d = _dev_u32(_words(n, 9))
+    d = dev_s32(_words(n, 9))
     out = Out()
     need = W.concat_work_bytes(n)
     work = torch.zeros(need, dtype=torch.uint8, device="cuda")
@@ -231,18 +224,11 @@ def test_graph_replay(W):
         W.crc32_concat(d_crc, None, n, o1.ptr, length=1456, last_len=1000, work=cwork)
         W.crc32_buffer(view, nbytes, o2.ptr, work=bwork)
 
-    cs = torch.cuda.Stream()
-    cs.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(cs):
-        call()
-    cs.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=cs):
-        call()
+    g, _ = capture(call)
     for salt in (1, 2):
         crc = _words(n, salt)
         data = O.synth_fill_np(nbytes, start_byte=1000 * salt)
-        d_crc.copy_(_dev_u32(crc))
+        d_crc.copy_(dev_s32(crc))
         view.copy_(torch.from_numpy(data).cuda())
         o1.t[1] = 0
         o2.t[1] = 0

@@ -9,42 +9,18 @@ import pytest
 
 import deliver_model as M
 import oracle as O
+from gpu_support import W_noinit as W  # noqa: F401 (fixture)
+from gpu_support import Bytes, Words, assert_bytes_equal, assert_no_data_error, capture, dev_s32, replay_each_then_together
+from gpu_support import u32
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DATA_ERROR_BITS = 0b101  # wtp_device_status: bit 0 (length > max), bit 2 (recv_len changed)
 MAXP, EMPTY, SENT, WSENT, GUARD, PAGE = M.MAXP, M.EMPTY, 12345, 0xA5, 64, 4096
 # wtp_deliver.hip: a wave of k_deliver_copy takes 256 vectors (4 KiB) per round, a workgroup
 # four of them, and the capped grid of 2048 workgroups 32 MiB of the stream per pass; a wave
 # keeps up to 256 prefix sums of a round in LDS
 WAVE_BYTES, GROUP_BYTES, PASS_BYTES, STAGED = 4096, 16384, 2048 * 16384, 256
-
-
-@pytest.fixture(scope="module")
-def W():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import wtp_crc32 as W
-    W.device_status(0, clear=True)
-    return W
-
-
-class Arr:
-    """A device array of n u32 or u64 words behind a view, with 4 guard words after it."""
-
-    def __init__(self, init, dtype, n=None):
-        self.np_t, self.guard = dtype, dtype(0x5A5A5A5A)
-        init = np.full(n, init, dtype=dtype) if n is not None else np.ascontiguousarray(init, dtype=dtype)
-        self.n = init.size
-        signed = np.int32 if dtype is np.uint32 else np.int64
-        self.buf = torch.from_numpy(np.concatenate([init, np.full(4, self.guard, dtype)]).view(signed)).cuda()
-        self.t = self.buf[:max(self.n, 1)]
-
-    def get(self):
-        h = self.buf.cpu().numpy().view(self.np_t)
-        assert (h[self.n:] == self.guard).all()  # nothing written past the array
-        return h[:self.n].copy()
 
 
 class Win:
@@ -56,17 +32,12 @@ class Win:
         self.sl_host = np.ascontiguousarray(slot_len, dtype=np.uint32)
         self.window = self.sl_host.size
         assert self.host.size == self.window * MAXP
-        self.lo = PAGE + img_off
-        self.buf = torch.full((self.lo + self.host.size + PAGE,), 0xC3, dtype=torch.uint8, device="cuda")
-        assert self.buf.data_ptr() % 16 == 0
-        self.buf[self.lo:self.lo + self.host.size].copy_(torch.from_numpy(self.host))
-        self.img = self.buf[self.lo:]
-        self.sl = Arr(self.sl_host, np.uint32)
+        self.mem = Bytes(self.host, off=img_off, front=PAGE, back=PAGE)  # the pages hold 0xC3
+        self.img = self.mem.t
+        self.sl = Words(self.sl_host)
 
     def check_untouched(self):
-        h = self.buf.cpu().numpy()
-        assert np.array_equal(h[self.lo:self.lo + self.host.size], self.host)
-        assert (h[:self.lo] == 0xC3).all() and (h[self.lo + self.host.size:] == 0xC3).all()
+        assert np.array_equal(self.mem.get(), self.host)
         assert np.array_equal(self.sl.get(), self.sl_host)
 
 
@@ -87,13 +58,11 @@ def run(W, w, max_slots=None, cap=None, off=0, phase=0, with_offs=True, with_len
     valid = w.sl_host[:window].astype(np.int64)
     if cap is None:
         cap = off + int(valid[valid <= MAXP].sum())
-    whole = torch.full((GUARD + phase + cap + GUARD,), WSENT, dtype=torch.uint8, device="cuda")
-    assert whole.data_ptr() % 16 == 0
-    stream = whole[GUARD + phase:]
-    offs, lens, counts = Arr(SENT, np.uint64, window), Arr(SENT, np.uint32, window), Arr(SENT, np.uint64, 4)
+    stream = Bytes(fill=WSENT, size=cap, off=phase, front=GUARD, back=GUARD, guard=WSENT)
+    offs, lens, counts = Words(SENT, window, np.uint64), Words(SENT, window), Words(SENT, 4, np.uint64)
     need = W.rx_deliver_work_bytes(window)
     work = torch.full((work_off + need,), 0xEE, dtype=torch.uint8, device="cuda")[work_off:]  # arbitrary contents
-    W.rx_deliver(w.img, w.sl.t, window, max_slots, stream, cap, off, offs.t if with_offs else None,
+    W.rx_deliver(w.img, w.sl.t, window, max_slots, stream.t, cap, off, offs.t if with_offs else None,
                  lens.t if with_lens else None, counts.t, work=work)
     torch.cuda.synchronize()
     copied = window > 0 and max_slots > 0
@@ -102,17 +71,13 @@ def run(W, w, max_slots=None, cap=None, off=0, phase=0, with_offs=True, with_len
                                                         cap, off, np.full(window, SENT, np.uint64),
                                                         np.full(window, SENT, np.uint32))
     assert counts.get().tolist() == want_counts.tolist()
-    got = whole.cpu().numpy()
-    lo = GUARD + phase
-    assert (got[:lo] == WSENT).all() and (got[lo + cap:] == WSENT).all()  # nothing outside the buffer
-    if not np.array_equal(got[lo:lo + cap], want):
-        bad = np.flatnonzero(got[lo:lo + cap] != want)
-        raise AssertionError(f"{bad.size} stream bytes differ, first at {bad[0]} (off {off}, phase {phase}, "
-                             f"delivered {int(want_counts[2])} bytes of {int(want_counts[0])} records)")
+    got = stream.get()  # nothing outside the buffer
+    assert_bytes_equal(got, want, 1, f"stream bytes: off {off}, phase {phase}, delivered {int(want_counts[2])} bytes of "
+                                     f"{int(want_counts[0])} records")
     assert np.array_equal(offs.get(), want_offs if with_offs else np.full(window, SENT, np.uint64))
     assert np.array_equal(lens.get(), want_lens if with_lens else np.full(window, SENT, np.uint32))
     w.check_untouched()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
     return want_counts, want
 
 
@@ -209,7 +174,7 @@ def test_stream_sizes_around_the_copy_kernels_groups(W):
 def test_window_size_zero(W):
     w = window_of(O.zipf_lengths(10))
     assert run(W, w, window=0, cap=100, off=7)[0].tolist() == [0, 0, 0, 0]
-    whole = Arr(SENT, np.uint64, 4)
+    whole = Words(SENT, 4, np.uint64)
     work = torch.empty(W.rx_deliver_work_bytes(0), dtype=torch.uint8, device="cuda")
     W.rx_deliver(None, None, 0, 5, None, 0, 0, None, None, whole.t, work=work)  # no pointer but d_counts and d_work
     torch.cuda.synchronize()
@@ -276,17 +241,10 @@ def test_graph_replay(W):
             self.off, self.max_slots = salt, n - 7 * salt
             self.cap = self.off + int(lens[:n - 60 * salt].sum())  # the capacity cuts before max_slots and the run do
             self.stream_buf = torch.empty(self.cap, dtype=torch.uint8, device="cuda")
-            self.offs, self.lens, self.counts = Arr(SENT, np.uint64, n), Arr(SENT, np.uint32, n), Arr(SENT, np.uint64, 4)
+            self.offs, self.lens, self.counts = Words(SENT, n, np.uint64), Words(SENT, n), Words(SENT, 4, np.uint64)
             self.work = torch.full((W.rx_deliver_work_bytes(n),), 0xEE, dtype=torch.uint8, device="cuda")
-            self.stream = torch.cuda.Stream()
             self.reset()
-            self.stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self.stream):
-                self.call()
-            self.stream.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=self.stream):
-                self.call()
+            self.graph, self.stream = capture(self.call)
             self.want = M.deliver(self.w.host, self.w.sl_host, n, self.max_slots, np.full(self.cap, WSENT, np.uint8), self.cap,
                                   self.off, np.full(n, SENT, np.uint64), np.full(n, SENT, np.uint32))
             assert 0 < self.want[3][0] < min(self.max_slots, self.want[3][1])
@@ -307,32 +265,12 @@ def test_graph_replay(W):
             assert np.array_equal(self.offs.get(), self.want[1]) and np.array_equal(self.lens.get(), self.want[2])
             assert self.counts.get().tolist() == self.want[3].tolist()
 
-    g = G(1)
-    for _ in range(3):
-        g.reset()
-        torch.cuda.synchronize()
-        g.graph.replay()
-        torch.cuda.synchronize()
-        g.check()
-    h, k = G(2), G(3)
-    for x in (g, h, k):
-        x.reset()
-    torch.cuda.synchronize()
-    for x in (h, k, g):
-        with torch.cuda.stream(x.stream):
-            x.graph.replay()
-    torch.cuda.synchronize()
-    for x in (g, h, k):
-        x.check()
+    for x in replay_each_then_together(G(1), [()] * 3, lambda: (G(2), G(3)), [()] * 3):
         x.w.check_untouched()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
 
 
 # ---- 9, 10. round trips ---------------------------------------------------------------------------
-def _s32(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
-
-
 class Sender:
     """2000 packed Zipf records built into datagrams by wtp_build_data_packets_var."""
 
@@ -345,9 +283,9 @@ class Sender:
         self.total = int(self.lens.sum())
         self.host = O.synth_fill_np(self.total, start_byte=3)
         self.wire = torch.full((n * stride,), WSENT, dtype=torch.uint8, device="cuda")
-        self.wl, self.crc = _s32(np.zeros(n)), _s32(np.zeros(n))
+        self.wl, self.crc = dev_s32(np.zeros(n)), dev_s32(np.zeros(n))
         W.build_data_packets_var(torch.from_numpy(self.host).cuda(), self.total,
-                                 torch.from_numpy(self.offs.view(np.int64)).cuda(), _s32(self.lens), n, seq0, self.wire,
+                                 torch.from_numpy(self.offs.view(np.int64)).cuda(), dev_s32(self.lens), n, seq0, self.wire,
                                  stride, self.wl, self.crc)
 
     def pick(self, idx):
@@ -368,23 +306,21 @@ def test_round_trip_one_batch(W):
     sl = torch.full((n,), -1, dtype=torch.int32, device="cuda")
     ok = torch.zeros(n, dtype=torch.uint8, device="cuda")
     W.accept_data_packets(ring, s.stride, wl, n, s.seq0, n, img, sl, ok)
-    whole = torch.full((GUARD + s.total + GUARD,), WSENT, dtype=torch.uint8, device="cuda")
-    offs, lens, counts = Arr(SENT, np.uint64, n), Arr(SENT, np.uint32, n), Arr(SENT, np.uint64, 4)
-    W.rx_deliver(img, sl, n, n, whole[GUARD:], s.total, 0, offs.t, lens.t, counts.t)
+    whole = Bytes(fill=WSENT, size=s.total, front=GUARD, back=GUARD, guard=WSENT)
+    offs, lens, counts = Words(SENT, n, np.uint64), Words(SENT, n), Words(SENT, 4, np.uint64)
+    W.rx_deliver(img, sl, n, n, whole.t, s.total, 0, offs.t, lens.t, counts.t)
     crc = torch.zeros(n, dtype=torch.int32, device="cuda")
-    W.crc32_batch_packed(whole[GUARD:], s.total, offs.t, lens.t, n, crc)
+    W.crc32_batch_packed(whole.t, s.total, offs.t, lens.t, n, crc)
     one = torch.zeros(1, dtype=torch.int32, device="cuda")
-    W.crc32_buffer(whole[GUARD:], s.total, one)
+    W.crc32_buffer(whole.t, s.total, one)
     torch.cuda.synchronize()
     assert bool((ok == 1).all())
     assert counts.get().tolist() == [n, n, s.total, s.total]
-    got = whole.cpu().numpy()
-    assert np.array_equal(got[GUARD:GUARD + s.total], s.host)
-    assert (got[:GUARD] == WSENT).all() and (got[GUARD + s.total:] == WSENT).all()
+    assert np.array_equal(whole.get(), s.host)
     assert np.array_equal(offs.get(), s.offs) and np.array_equal(lens.get(), s.lens)
-    assert torch.equal(crc, s.crc) and np.array_equal(crc.cpu().numpy().view(np.uint32), O.batch_var(s.host, s.offs, s.lens))
-    assert int(one.cpu().numpy().view(np.uint32)[0]) == O.crc32(s.host)
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert torch.equal(crc, s.crc) and np.array_equal(u32(crc), O.batch_var(s.host, s.offs, s.lens))
+    assert int(u32(one)[0]) == O.crc32(s.host)
+    assert_no_data_error(W)
 
 
 def test_round_trip_two_rounds_with_a_loss(W):
@@ -397,27 +333,25 @@ def test_round_trip_two_rounds_with_a_loss(W):
     first = [i for i in np.random.default_rng(10).permutation(n).tolist() if i not in lost]
     img = torch.full((n * MAXP,), 0x3C, dtype=torch.uint8, device="cuda")
     sl = torch.full((n,), -1, dtype=torch.int32, device="cuda")
-    whole = torch.full((GUARD + s.total + GUARD,), WSENT, dtype=torch.uint8, device="cuda")
-    offs, lens = Arr(SENT, np.uint64, n), Arr(SENT, np.uint32, n)
-    c1, c2 = Arr(SENT, np.uint64, 4), Arr(SENT, np.uint64, 4)
+    whole = Bytes(fill=WSENT, size=s.total, front=GUARD, back=GUARD, guard=WSENT)
+    offs, lens = Words(SENT, n, np.uint64), Words(SENT, n)
+    c1, c2 = Words(SENT, 4, np.uint64), Words(SENT, 4, np.uint64)
     ring, wl = s.pick(first)
     ok = torch.zeros(len(first), dtype=torch.uint8, device="cuda")
     W.accept_data_packets(ring, s.stride, wl, len(first), s.seq0, n, img, sl, ok)
-    W.rx_deliver(img, sl, n, n, whole[GUARD:], s.total, 0, offs.t, lens.t, c1.t)
+    W.rx_deliver(img, sl, n, n, whole.t, s.total, 0, offs.t, lens.t, c1.t)
     torch.cuda.synchronize()
     k, run_, pk, prun = c1.get().tolist()
     assert bool((ok == 1).all()) and k == run_ == 300 and pk == prun == int(s.lens[:300].sum())
-    got = whole.cpu().numpy()
-    assert np.array_equal(got[GUARD:GUARD + pk], s.host[:pk]) and (got[GUARD + pk:] == WSENT).all()
+    got = whole.get()
+    assert np.array_equal(got[:pk], s.host[:pk]) and (got[pk:] == WSENT).all()
     # the window moves by k: the image, slot_len and the metadata arrays from slot k on
     ring, wl = s.pick(lost[::-1])
     ok = torch.zeros(3, dtype=torch.uint8, device="cuda")
     W.accept_data_packets(ring, s.stride, wl, 3, s.seq0 + k, n - k, img[k * MAXP:], sl[k:], ok)
-    W.rx_deliver(img[k * MAXP:], sl[k:], n - k, n - k, whole[GUARD:], s.total, pk, offs.t[k:], lens.t[k:], c2.t)
+    W.rx_deliver(img[k * MAXP:], sl[k:], n - k, n - k, whole.t, s.total, pk, offs.t[k:], lens.t[k:], c2.t)
     torch.cuda.synchronize()
     assert bool((ok == 1).all()) and c2.get().tolist() == [n - k, n - k, s.total - pk, s.total - pk]
-    got = whole.cpu().numpy()
-    assert np.array_equal(got[GUARD:GUARD + s.total], s.host)
-    assert (got[:GUARD] == WSENT).all() and (got[GUARD + s.total:] == WSENT).all()
+    assert np.array_equal(whole.get(), s.host)
     assert np.array_equal(offs.get(), s.offs) and np.array_equal(lens.get(), s.lens)
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)

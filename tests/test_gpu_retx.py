@@ -10,62 +10,14 @@ import pytest
 
 import oracle as O
 import retx_model as M
+from gpu_support import W  # noqa: F401 (fixture)
+from gpu_support import DATA_ERROR_BITS, Bytes, DevEnd, Words, assert_no_data_error, capture, dev_s32, s32, u32
+from gpu_support import datagram_ring as _ring
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DATA_ERROR_BITS = 0b101  # wtp_device_status: bit 0 (length > max), bit 2 (recv_len changed)
 MAXP, STRIDE, SENT = M.MAXP, M.STRIDE, 12345
-
-
-@pytest.fixture(scope="module")
-def W():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import wtp_crc32 as W
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
-    W.device_status(0, clear=True)
-    return W
-
-
-def _s32(a):
-    return np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)
-
-
-class Words:
-    """A u32 device array of n words behind a view, with 4 guard words (0x5A5A5A5A) after it."""
-
-    def __init__(self, init, n=None):
-        init = np.full(n, init, dtype=np.uint32) if n is not None else np.ascontiguousarray(init, dtype=np.uint32)
-        self.n = init.size
-        self.buf = torch.from_numpy(_s32(np.concatenate([init, np.full(4, 0x5A5A5A5A, np.uint32)]))).cuda()
-        self.t = self.buf[:max(self.n, 1)]
-
-    def get(self):
-        h = self.buf.cpu().numpy().view(np.uint32)
-        assert (h[self.n:] == 0x5A5A5A5A).all()  # nothing written past the array
-        return h[:self.n].copy()
-
-
-def _bytes(host, off=0):
-    """Device copy of a host byte array at byte offset `off` of its allocation; 16 guard
-    bytes (0xC3) after it.  Returns (view, whole buffer)."""
-    buf = torch.full((host.size + off + 16,), 0xC3, dtype=torch.uint8, device="cuda")
-    buf[off:off + host.size].copy_(torch.from_numpy(host))
-    return buf[off:off + max(host.size, 1)], buf
-
-
-def _ring(dgrams, stride, salt=0):
-    """(ring, recv_len): `dgrams` in `stride`-byte slots (cut at the slot's end; recv_len
-    keeps the full length); the slot bytes past a datagram are random."""
-    rng = np.random.default_rng(len(dgrams) * 131 + stride + salt)
-    ring = rng.integers(0, 256, len(dgrams) * stride, dtype=np.uint8)
-    rl = np.zeros(len(dgrams), dtype=np.uint32)
-    for i, d in enumerate(dgrams):
-        cut = min(len(d), stride)
-        ring[i * stride:i * stride + cut] = np.frombuffer(d[:cut], dtype=np.uint8)
-        rl[i] = len(d)
-    return ring, rl
 
 
 # ---- ingest --------------------------------------------------------------------------------
@@ -73,7 +25,8 @@ def dev_ingest(W, ring, rl, stride, mode, seq0, inflight, acked, ring_off=0, wit
     """One wtp_tx_ingest_acks from the entry state `acked` (numpy), with the guard and
     untouched-input checks; returns the device's (ok, hit, acked, counts) as numpy."""
     n = rl.size
-    d, dbuf = _bytes(ring, ring_off)
+    dbuf = Bytes(ring, off=ring_off)  # 16 guard bytes (0xC3) after it
+    d = dbuf.t
     r, ok, hit = Words(rl), torch.full((n + 16,), 7, dtype=torch.uint8, device="cuda"), Words(SENT, n)
     st, counts = Words(acked), Words(0x77777777, 2)
     W.tx_ingest_acks(d, stride, r.t, n, mode, seq0, inflight, st.t, ok, hit.t if with_hit else None, counts.t)
@@ -81,10 +34,10 @@ def dev_ingest(W, ring, rl, stride, mode, seq0, inflight, acked, ring_off=0, wit
     assert W.LIB.wtp_last_kernel().decode() == ("k_tx_lead" if mode == M.SELECTIVE else "k_tx_window")
     got_ok = ok.cpu().numpy()
     assert (got_ok[n:] == 7).all()
-    assert np.array_equal(r.get(), rl) and (dbuf[dbuf.numel() - 16:] == 0xC3).all()
-    assert torch.equal(dbuf[ring_off:ring_off + ring.size].cpu(), torch.from_numpy(ring))  # the ring is only read
+    assert np.array_equal(r.get(), rl)
+    assert np.array_equal(dbuf.get(), ring)  # the ring is only read
     # this call alone never sets a data-error flag, whatever the ring holds
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
     if n:  # d_ok is what wtp_crc32_verify_batch writes for the same ring
         ok2 = torch.full((n,), 9, dtype=torch.uint8, device="cuda")
         W.verify_batch(d, stride, r.t, n, ok2)
@@ -244,10 +197,10 @@ def retx(W, src, acked, sent, now, timeout, flags, max_sel, stride=STRIDE, wire_
     if emitted:  # ... and intact for a receiver
         ok = torch.zeros(emitted, dtype=torch.uint8, device="cuda")
         ring = rows[:emitted].contiguous()
-        W.verify_batch(ring, stride, torch.from_numpy(_s32(lens)).cuda(), emitted, ok)
+        W.verify_batch(ring, stride, dev_s32(lens), emitted, ok)
         torch.cuda.synchronize()
         assert bool(ok.all())
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
     return w_sel, w_sent, (emitted, due)
 
 
@@ -353,96 +306,31 @@ def test_graph_replay(W):
         W.tx_build_retransmit(src.dev, src.total, seq0, inflight, acked_t, sent_t, now, TIMEOUT, 0, wire, STRIDE, max_sel,
                               sel_t, wlen_t, c2, work=work)
 
-    cs = torch.cuda.Stream()
-    cs.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(cs):
-        call()
-    cs.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=cs):
-        call()
+    g, _ = capture(call)
     for salt in (1, 2):
         acked = (rng.random(inflight) < 0.3).astype(np.uint32)
         sent = (now - rng.integers(0, 1000, inflight)).astype(np.uint32)
         seqs = (seq0 + rng.integers(-2, inflight + 2, n)) & M.M32
         ring, rl = M.make_ring([M.ack_datagram(int(s), checksum=int(k % 13 == 0)) for k, s in enumerate(seqs)], 16)
         ring_t.copy_(torch.from_numpy(ring))
-        acked_t.copy_(torch.from_numpy(_s32(acked)))
-        sent_t.copy_(torch.from_numpy(_s32(sent)))
+        acked_t.copy_(torch.from_numpy(s32(acked)))
+        sent_t.copy_(torch.from_numpy(s32(sent)))
         wire.fill_(0xA5)
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
         w_ok, w_hit, w_acked, w_c1 = M.ingest(ring, 16, rl, M.SELECTIVE, seq0, inflight, acked)
         w_sel, w_dg, w_sent, w_c2 = M.retransmit(src.host, src.total, seq0, inflight, w_acked, sent, now, TIMEOUT, 0, max_sel)
-        u = lambda t: t.cpu().numpy().view(np.uint32)  # noqa: E731
-        assert np.array_equal(ok_t.cpu().numpy(), w_ok) and np.array_equal(u(hit_t), w_hit)
-        assert np.array_equal(u(acked_t), w_acked) and tuple(u(c1)) == w_c1 and tuple(u(c2)) == w_c2
-        assert np.array_equal(u(sent_t), w_sent) and np.array_equal(u(sel_t)[:w_c2[0]], w_sel)
+        assert np.array_equal(ok_t.cpu().numpy(), w_ok) and np.array_equal(u32(hit_t), w_hit)
+        assert np.array_equal(u32(acked_t), w_acked) and tuple(u32(c1)) == w_c1 and tuple(u32(c2)) == w_c2
+        assert np.array_equal(u32(sent_t), w_sent) and np.array_equal(u32(sel_t)[:w_c2[0]], w_sel)
         got = wire.view(max_sel, STRIDE).cpu().numpy()
         assert 0 < w_c2[0] and all(got[k, :len(d)].tobytes() == d for k, d in enumerate(w_dg))
         assert (got[w_c2[0]:] == 0xA5).all()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
 
 
 # ---- end to end on the device -------------------------------------------------------------------
-class DevEnd:
-    """Both windows on the device, behind the calls of retx_model.transfer: no payload byte
-    crosses to the host (it reads back verdicts, 8 header bytes per datagram and counts)."""
-
-    def __init__(self, W, src, total, nchunks, window, seq_base):
-        self.W, self.src, self.total, self.window, self.seq_base = W, src, total, window, seq_base
-        z = lambda k, v=0: torch.full((k,), v, dtype=torch.int32, device="cuda")  # noqa: E731
-        self.acked, self.sent, self.slot_len = z(nchunks + window), z(nchunks + window), z(nchunks + window, -1)
-        self.img = torch.full(((nchunks + window) * MAXP,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.counts, self.ack = z(2), z(1)
-        self.retx_wire = torch.zeros((0, STRIDE), dtype=torch.uint8, device="cuda")
-        self.retx_len = z(0)
-
-    def seq(self, chunk):
-        return (self.seq_base + chunk) & M.M32
-
-    def send(self, c0, cnt, now):
-        wire = torch.zeros((cnt, STRIDE), dtype=torch.uint8, device="cuda")
-        wlen = torch.zeros(cnt, dtype=torch.int32, device="cuda")
-        if cnt:
-            nbytes = min(self.total, (c0 + cnt) * MAXP) - c0 * MAXP
-            self.W.build_data_packets(self.src[c0 * MAXP:], nbytes, self.seq(c0), wire, STRIDE, wlen)
-            self.sent[c0:c0 + cnt] = int(_s32([now])[0])
-        self.wire, self.wlen = torch.cat([wire, self.retx_wire]), torch.cat([wlen, self.retx_len])
-        return self.wire.shape[0]
-
-    def accept(self, idx, rbase):
-        n = idx.size
-        sel = torch.from_numpy(idx.astype(np.int64)).cuda()
-        ring, rl = self.wire[sel].contiguous(), self.wlen[sel].contiguous()
-        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
-        self.W.accept_data_packets(ring if n else ok, STRIDE, rl if n else self.ack, n, self.seq(rbase), self.window,
-                                   self.img[rbase * MAXP:], self.slot_len[rbase:], ok, None, self.ack)
-        hdr = np.ascontiguousarray(ring[:, :8].cpu().numpy()).reshape(n, 8).view(">u4")
-        return (ok[:n].cpu().numpy(), hdr[:, 0].astype(np.uint32), hdr[:, 1].astype(np.uint32),
-                int(self.ack.cpu().numpy().view(np.uint32)[0]))
-
-    def ingest(self, acks, mode, sbase, inflight):
-        ring, rl = M.make_ring(acks, 16)
-        n = rl.size
-        d = torch.from_numpy(ring).cuda()
-        r = torch.from_numpy(_s32(rl)).cuda() if n else self.ack
-        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
-        self.W.tx_ingest_acks(d, 16, r, n, mode, self.seq(sbase), inflight, self.acked[sbase:], ok, None, self.counts)
-        return int(self.counts[0].item())
-
-    def retransmit(self, sbase, inflight, now, timeout, flags, max_sel):
-        wire = torch.zeros((max_sel, STRIDE), dtype=torch.uint8, device="cuda")
-        sel, wlen = (torch.zeros(max_sel, dtype=torch.int32, device="cuda") for _ in range(2))
-        self.W.tx_build_retransmit(self.src[sbase * MAXP:], self.total - sbase * MAXP, self.seq(sbase), inflight,
-                                   self.acked[sbase:], self.sent[sbase:], now, timeout, flags, wire, STRIDE, max_sel, sel,
-                                   wlen, self.counts)
-        e = int(self.counts[0].item())
-        self.retx_wire, self.retx_len = wire[:e], wlen[:e]
-        return sel[:e].cpu().numpy()
-
-
 @pytest.mark.parametrize("mode,seq_base", [(M.SELECTIVE, 0), (M.SELECTIVE, 0xFFFFFF80), (M.CUMULATIVE, 0),
                                            (M.CUMULATIVE, 0xFFFFFF80)])
 def test_end_to_end_transfer_on_the_device(W, mode, seq_base):
@@ -464,8 +352,8 @@ def test_end_to_end_transfer_on_the_device(W, mode, seq_base):
     assert torch.equal(end.img[:total], src) and bool((end.img[total:nchunks * MAXP] == 0xA5).all())
     crc = torch.zeros(1, dtype=torch.int32, device="cuda")
     W.crc32_buffer(end.img, total, crc)
-    assert int(crc.cpu().numpy().view(np.uint32)[0]) == O.crc32(host)
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert int(u32(crc)[0]) == O.crc32(host)
+    assert_no_data_error(W)
 
 
 # ---- ingest at the sizes where its kernels change behaviour -----------------------------------

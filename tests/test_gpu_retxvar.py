@@ -13,12 +13,13 @@ import buildvar_model as B
 import oracle as O
 import retx_model as R
 import retxvar_model as M
-from test_gpu_buildvar import Batch, Words, packed
+from gpu_support import W_noinit as W  # noqa: F401 (fixture)
+from gpu_support import Batch, Bytes, DevStreamEnd, Words, assert_bytes_equal, assert_no_data_error, capture, dev_s32
+from gpu_support import packed, replay_each_then_together, u32
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DATA_ERROR_BITS = 0b101  # wtp_device_status: bit 0 (length > max), bit 2 (recv_len changed)
 MAXP, STRIDE, M32, SENT, WSENT, GUARD = M.MAXP, M.STRIDE, M.M32, 12345, 0xA5, 64
 NOW, TIMEOUT = 10_000, 500
 OLD, FRESH = NOW - TIMEOUT - 1, NOW - TIMEOUT  # a timer that is due, and one that is just not
@@ -32,23 +33,6 @@ OLD, FRESH = NOW - TIMEOUT - 1, NOW - TIMEOUT  # a timer that is due, and one th
 # 163 841 (32 -> 64); above 64 * 5120 = 327 680 a wave takes a second round.
 CAP_WAVES = 5120
 THRESHOLDS = [CAP_WAVES << j for j in range(6)]
-
-
-@pytest.fixture(scope="module")
-def W():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import wtp_crc32 as W
-    W.device_status(0, clear=True)
-    return W
-
-
-def _s32(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def _u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 def state(n, due, rng=None):
@@ -71,13 +55,12 @@ def run(W, b, acked, sent, max_sel, seq0=0, stride=STRIDE, ring_off=0, now=NOW, 
     model's (wire, sel, wire_len, crc, sent, counts) and the state arrays after the call."""
     inflight = b.n if inflight is None else inflight
     rows = max(max_sel, 1)
-    whole = torch.full((GUARD + ring_off + rows * stride + GUARD,), WSENT, dtype=torch.uint8, device="cuda")
-    assert whole.data_ptr() % 16 == 0
+    ring = Bytes(fill=WSENT, size=rows * stride, off=ring_off, front=GUARD, back=GUARD, guard=WSENT)
     d_acked, d_sent, counts = Words(acked), Words(sent), Words(SENT, 2)
     d_out = [Words(SENT, rows) if on else None for on in outs]
     work = torch.empty(W.tx_work_bytes(inflight, max_sel), dtype=torch.uint8, device="cuda")
     W.tx_build_retransmit_var(b.base, b.base_bytes, b.o, b.l.t, seq0, inflight, d_acked.t, d_sent.t, now, timeout, flags,
-                              whole[GUARD + ring_off:], stride, max_sel, *(w.t if w else None for w in d_out), counts.t,
+                              ring.t, stride, max_sel, *(w.t if w else None for w in d_out), counts.t,
                               work=work)
     torch.cuda.synchronize()
     assert W.LIB.wtp_last_kernel().decode() == ("k_tx_emit_var" if min(inflight, max_sel) else "k_tx_select")
@@ -85,18 +68,13 @@ def run(W, b, acked, sent, max_sel, seq0=0, stride=STRIDE, ring_off=0, now=NOW, 
     want = M.retransmit_var(b.host, b.base_bytes, b.offs, b.lens, seq0, inflight, acked, sent, now, timeout, flags,
                             np.full(rows * stride, WSENT, np.uint8), stride, max_sel, *prior, vectorised=vectorised)
     assert tuple(counts.get().tolist()) == want[5], (counts.get(), want[5])
-    got = whole.cpu().numpy()
-    lo = GUARD + ring_off
-    assert (got[:lo] == WSENT).all() and (got[lo + rows * stride:] == WSENT).all()  # nothing outside the ring
-    if not np.array_equal(got[lo:lo + rows * stride], want[0]):
-        bad = np.flatnonzero(got[lo:lo + rows * stride] != want[0])
-        raise AssertionError(f"{bad.size} wire bytes differ, first in entry {bad[0] // stride} at byte {bad[0] % stride} "
-                             f"(emitted {want[5][0]}, max_sel {max_sel}, inflight {inflight})")
+    got = ring.get()  # nothing outside the ring
+    assert_bytes_equal(got, want[0], stride, f"ring entries: emitted {want[5][0]}, max_sel {max_sel}, inflight {inflight}")
     for name, w, x in zip(("sel", "wire_len", "crc_out"), d_out, want[1:4]):
         assert w is None or np.array_equal(w.get(), x), name
     assert np.array_equal(d_sent.get(), want[4]) and np.array_equal(d_acked.get(), acked)
     b.check_untouched()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
     return want, d_sent.get()
 
 
@@ -312,8 +290,8 @@ def test_chunked_buffer_equals_the_fixed_call(W, short):
         ring = torch.full((n * STRIDE,), WSENT, dtype=torch.uint8, device="cuda")
         a, s, sel, wl, counts = Words(acked), Words(sent), Words(SENT, n), Words(SENT, n), Words(SENT, 2)
         if var:
-            W.tx_build_retransmit_var(src, total, torch.from_numpy(offs.view(np.int64)).cuda(), _s32(lens), 0xFFFFFF00, n, a.t,
-                                      s.t, NOW, TIMEOUT, 0, ring, STRIDE, n, sel.t, wl.t, None, counts.t)
+            W.tx_build_retransmit_var(src, total, torch.from_numpy(offs.view(np.int64)).cuda(), dev_s32(lens), 0xFFFFFF00, n,
+                                      a.t, s.t, NOW, TIMEOUT, 0, ring, STRIDE, n, sel.t, wl.t, None, counts.t)
         else:
             W.tx_build_retransmit(src, total, 0xFFFFFF00, n, a.t, s.t, NOW, TIMEOUT, 0, ring, STRIDE, n, sel.t, wl.t, counts.t)
         torch.cuda.synchronize()
@@ -335,16 +313,16 @@ def test_400000_short_records_all_due(W):
     seq0 = 0xFFFF0000
     want = torch.full((n * STRIDE,), WSENT, dtype=torch.uint8, device="cuda")
     W.build_data_packets_var(b.base, b.base_bytes, b.o, b.l.t, n, seq0, want, STRIDE)
-    whole = torch.full((GUARD + n * STRIDE + GUARD,), WSENT, dtype=torch.uint8, device="cuda")
+    whole = Bytes(fill=WSENT, size=n * STRIDE, front=GUARD, back=GUARD, guard=WSENT)
     acked, sent, counts = Words(0, n), Words(OLD, n), Words(SENT, 2)
     sel, wl, crc = Words(SENT, n), Words(SENT, n), Words(SENT, n)
-    W.tx_build_retransmit_var(b.base, b.base_bytes, b.o, b.l.t, seq0, n, acked.t, sent.t, NOW, TIMEOUT, 0, whole[GUARD:], STRIDE,
+    W.tx_build_retransmit_var(b.base, b.base_bytes, b.o, b.l.t, seq0, n, acked.t, sent.t, NOW, TIMEOUT, 0, whole.t, STRIDE,
                               n, sel.t, wl.t, crc.t, counts.t)
     torch.cuda.synchronize()
-    assert torch.equal(whole[GUARD:GUARD + n * STRIDE], want)
-    slots = whole[GUARD:GUARD + n * STRIDE].view(n, STRIDE)
+    assert torch.equal(whole.payload, want)
+    slots = whole.payload.view(n, STRIDE)
     assert bool((slots[:, 24:] == WSENT).all()) and bool((slots[:, 0:4] == torch.tensor([0, 0, 0, 2], device="cuda")).all())
-    assert bool((whole[:GUARD] == WSENT).all()) and bool((whole[GUARD + n * STRIDE:] == WSENT).all())
+    whole.check_guards()
     assert counts.get().tolist() == [n, n] and np.array_equal(sel.get(), np.arange(n)) and (sent.get() == NOW).all()
     assert np.array_equal(wl.get(), lens + 16) and np.array_equal(crc.get(), O.batch_var(base, offs, lens))
     head = slots[:, :16].cpu().numpy().view(">u4")  # the headers against the oracle
@@ -369,22 +347,20 @@ def test_offsets_above_4_gib(W):
     n = 8
     acked = np.array([0, 0, 1, 0, 0, 1, 0, 0], np.uint32)
     sent = np.full(n, OLD, np.uint32)
-    whole = torch.full((GUARD + n * STRIDE + GUARD,), WSENT, dtype=torch.uint8, device="cuda")
+    whole = Bytes(fill=WSENT, size=n * STRIDE, front=GUARD, back=GUARD, guard=WSENT)
     sel, wl, crc, dl, counts = Words(SENT, n), Words(SENT, n), Words(SENT, n), Words(lens), Words(SENT, 2)
     da, ds = Words(acked), Words(sent)
     do = torch.from_numpy(offs.view(np.int64)).cuda()
-    W.tx_build_retransmit_var(big, top + tail, do, dl.t, 0xFFFFFFFC, n, da.t, ds.t, NOW, TIMEOUT, 0, whole[GUARD:], STRIDE, n,
+    W.tx_build_retransmit_var(big, top + tail, do, dl.t, 0xFFFFFFFC, n, da.t, ds.t, NOW, TIMEOUT, 0, whole.t, STRIDE, n,
                               sel.t, wl.t, crc.t, counts.t)
     torch.cuda.synchronize()
     want = M.retransmit_var(host, win + tail, offs - np.uint64(top - win), lens, 0xFFFFFFFC, n, acked, sent, NOW, TIMEOUT, 0,
                             np.full(n * STRIDE, WSENT, np.uint8), STRIDE, n, *(np.full(n, SENT, np.uint32) for _ in range(3)))
-    got = whole.cpu().numpy()
-    assert np.array_equal(got[GUARD:GUARD + n * STRIDE], want[0])
-    assert (got[:GUARD] == WSENT).all() and (got[GUARD + n * STRIDE:] == WSENT).all()
+    assert np.array_equal(whole.get(), want[0])
     assert np.array_equal(sel.get(), want[1]) and np.array_equal(wl.get(), want[2]) and np.array_equal(crc.get(), want[3])
     assert np.array_equal(ds.get(), want[4]) and tuple(counts.get().tolist()) == want[5] == (6, 6)
     assert want[2][:6].tolist() == [1472, 1472, 21, 1472, 33, 116]
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    assert_no_data_error(W)
 
 
 # ---- 8. graphs ---------------------------------------------------------------------------------------------------
@@ -411,15 +387,10 @@ def test_graph_replay(W):
             self.ring = torch.empty(n * STRIDE, dtype=torch.uint8, device="cuda")
             self.sel, self.wl, self.crc = Words(SENT, n), Words(SENT, n), Words(SENT, n)
             self.work = torch.empty(W.tx_work_bytes(n, n), dtype=torch.uint8, device="cuda")
-            self.stream = torch.cuda.Stream()
-            self.stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self.stream):  # a first run outside the capture: the zeroed ring holds no ACK,
-                self.call()                       # and every slot is emitted, so every timer becomes 77
-            self.stream.synchronize()
+            # capture's first run outside the capture: the zeroed ring holds no ACK, and every slot is emitted,
+            # so every timer becomes 77
+            self.graph, self.stream = capture(self.call)
             self.sent[:] = 77
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=self.stream):
-                self.call()
 
         def call(self):
             W.tx_ingest_acks(self.acks, 16, self.rl, nack, R.SELECTIVE, self.seq0, n, self.d_acked.t, self.ok, None,
@@ -451,32 +422,16 @@ def test_graph_replay(W):
             assert np.array_equal(self.d_acked.get(), self.acked) and np.array_equal(self.d_sent.get(), self.sent)
             self.b.check_untouched()
 
-    g = G(1)
-    for turn in range(3):
-        g.reset(turn)
-        torch.cuda.synchronize()
-        g.graph.replay()
-        torch.cuda.synchronize()
-        g.check()
-    h, k = G(2), G(3)
-    for x in (g, h, k):
-        x.reset(7)
-    torch.cuda.synchronize()
-    for x in (h, k, g):
-        with torch.cuda.stream(x.stream):
-            x.graph.replay()
-    torch.cuda.synchronize()
-    for x in (g, h, k):
-        x.check()
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    replay_each_then_together(G(1), [(0,), (1,), (2,)], lambda: (G(2), G(3)), [(7,)] * 3)
+    assert_no_data_error(W)
 
 
 # ---- 9. the sender-window stream loop ------------------------------------------------------------------------------
-class DevEnd:
+class DevVarEnd:
     """Both ends of retxvar_model.stream_rounds on the device.  The sender keeps two (acked,
     sent_ms) pairs of `window` entries and the record arrays, and no wire image: a round's ring
-    is what wtp_tx_build_retransmit_var built from the records.  The receiver is the one of
-    tests/test_gpu_advance.py's DevStreamEnd: accept -> ACKs -> deliver -> rx_advance over two
+    is what wtp_tx_build_retransmit_var built from the records.  The receiver, `rx`, is
+    gpu_support's DevStreamEnd over that ring: accept -> ACKs -> deliver -> rx_advance over two
     (img, slot_len) pairs.  Two synchronisations per round: one behind the sender's call, to
     read its counts and selection; one behind the receiver's calls and the sender's ingest ->
     tx_advance that follow them on the stream, to read deliver's counts and the advance (seq0
@@ -486,22 +441,13 @@ class DevEnd:
         self.W, self.total, self.seq0, self.window = W, total, seq0, window
         z = lambda k, v=0: torch.full((k,), v, dtype=torch.int32, device="cuda")  # noqa: E731
         self.base = torch.from_numpy(host).cuda()
-        self.o, self.l = torch.from_numpy(offs.view(np.int64)).cuda(), _s32(lens)
+        self.o, self.l = torch.from_numpy(offs.view(np.int64)).cuda(), dev_s32(lens)
         fill0 = int(np.array([(M.STREAM_NOW0 - M.STREAM_TIMEOUT - 1) & M32], np.uint32).view(np.int32)[0])
         self.acked, self.sent = [z(window), z(window)], [z(window, fill0), z(window, fill0)]
         self.ring = torch.full((window * STRIDE,), WSENT, dtype=torch.uint8, device="cuda")
         self.sel, self.wl, self.txc, self.adv = z(window), z(window), z(2), z(2)
         self.work = torch.empty(W.tx_work_bytes(window, window), dtype=torch.uint8, device="cuda")
-        self.img = [torch.full((window * MAXP,), 0x3C, dtype=torch.uint8, device="cuda") for _ in range(2)]
-        self.sl = [z(window, -1), z(window, -1)]
-        self.whole = torch.full((64 + total + 64,), WSENT, dtype=torch.uint8, device="cuda")
-        self.counts = torch.zeros(4, dtype=torch.int64, device="cuda")
-        self.ack_counts = z(2)
-        self.offs_out = torch.zeros(window, dtype=torch.int64, device="cuda")
-        self.lens_out = z(window)
-        self.dwork = torch.empty(W.rx_deliver_work_bytes(window), dtype=torch.uint8, device="cuda")
-        self.ack_ring = torch.zeros((window, 16), dtype=torch.uint8, device="cuda")
-        self.offs, self.lens = [], []
+        self.rx = DevStreamEnd(W, self.ring, self.wl, window, STRIDE, seq0, window, total)
 
     def emit(self, sbase, inflight, now, timeout):
         w = self.window
@@ -509,39 +455,26 @@ class DevEnd:
                                        self.acked[0], self.sent[0], now, timeout, 0, self.ring, STRIDE, w, self.sel, self.wl,
                                        None, self.txc, work=self.work)
         torch.cuda.synchronize()
-        counts = tuple(int(c) for c in _u32(self.txc))
-        return _u32(self.sel[:counts[0]]), counts
+        counts = tuple(int(c) for c in u32(self.txc))
+        return u32(self.sel[:counts[0]]), counts
 
     def receive(self, idx, rbase, off, aidx, sbase, inflight, fill_ms):
-        W, w, n, na = self.W, self.window, idx.size, aidx.size
-        pick = torch.from_numpy(idx.astype(np.int64)).cuda()
-        ok = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
-        ring = self.ring.view(w, STRIDE)[pick].contiguous().view(-1) if n else ok  # n == 0: any pointer
-        rl = self.wl[pick].contiguous() if n else self.ack_counts
-        seq = (self.seq0 + rbase) & M32
-        W.accept_data_packets(ring, STRIDE, rl, n, seq, w, self.img[0], self.sl[0], ok)
-        W.rx_build_acks(ring, STRIDE, rl, n, A.SELECTIVE, seq, w, ok, None, None, self.ack_ring, 16, 0, w, None,
-                        self.ack_counts)
-        W.rx_deliver(self.img[0], self.sl[0], w, w, self.whole[64:], self.total, off, self.offs_out, self.lens_out,
-                     self.counts, work=self.dwork)
-        W.rx_advance(self.img[0], self.sl[0], w, self.counts, self.img[1], self.sl[1])
-        self.img.reverse()
-        self.sl.reverse()
-        acks = self.ack_ring[torch.from_numpy(aidx.astype(np.int64)).cuda()].contiguous() if na else ok
-        arl = torch.full((max(na, 1),), 16, dtype=torch.int32, device="cuda")
+        W, w, na = self.W, self.window, aidx.size
         aok = torch.zeros(max(na, 1), dtype=torch.uint8, device="cuda")
-        W.tx_ingest_acks(acks, 16, arl, na, R.SELECTIVE, (self.seq0 + sbase) & M32, inflight, self.acked[0], aok, None, self.adv)
-        W.tx_advance(self.acked[0], self.sent[0], w, self.adv, fill_ms, self.acked[1], self.sent[1])
-        self.acked.reverse()
-        self.sent.reverse()
-        torch.cuda.synchronize()
-        counts = self.counts.cpu().numpy().view(np.uint64)
-        k = int(counts[0])
-        assert bool(ok[:n].all()) and _u32(self.ack_counts).tolist() == [n, n]  # every arrival is intact and answered
+
+        def ingest_and_slide():
+            pick = torch.from_numpy(aidx.astype(np.int64)).cuda()
+            acks = self.rx.ack_ring[pick].contiguous() if na else aok  # na == 0: any pointer
+            arl = torch.full((max(na, 1),), 16, dtype=torch.int32, device="cuda")
+            W.tx_ingest_acks(acks, 16, arl, na, R.SELECTIVE, (self.seq0 + sbase) & M32, inflight, self.acked[0], aok, None,
+                             self.adv)
+            W.tx_advance(self.acked[0], self.sent[0], w, self.adv, fill_ms, self.acked[1], self.sent[1])
+            self.acked.reverse()
+            self.sent.reverse()
+
+        counts = self.rx.round(idx, rbase, off, then=ingest_and_slide)
         assert bool(aok[:na].all())
-        self.offs += self.offs_out[:k].cpu().numpy().view(np.uint64).tolist()
-        self.lens += _u32(self.lens_out[:k]).tolist()
-        return tuple(int(c) for c in counts), int(_u32(self.adv)[0])
+        return tuple(int(c) for c in counts), int(u32(self.adv)[0])
 
 
 def test_sender_window_stream_loop(W):
@@ -552,14 +485,13 @@ def test_sender_window_stream_loop(W):
     assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()  # accept's verify and the CRC call, not the sender's calls
     lens, offs, total, host = M.stream_records()
     want = M.stream_rounds(M.ModelEnd(host, total, offs, lens, M.STREAM_SEQ0, M.STREAM_WINDOW))
-    end = DevEnd(W, host, total, offs, lens, M.STREAM_SEQ0, M.STREAM_WINDOW)
+    end = DevVarEnd(W, host, total, offs, lens, M.STREAM_SEQ0, M.STREAM_WINDOW)
     got = M.stream_rounds(end)
     assert got == want and len(got) == M.STREAM_ROUNDS <= M.STREAM_MAX_ROUNDS
-    whole = end.whole.cpu().numpy()
-    assert np.array_equal(whole[64:64 + total], host) and (whole[:64] == WSENT).all() and (whole[64 + total:] == WSENT).all()
-    assert np.array_equal(np.array(end.offs, np.uint64), offs) and np.array_equal(np.array(end.lens, np.uint32), lens)
+    assert np.array_equal(end.rx.whole.get(), host)  # between 64 guard bytes of 0xA5 on both sides
+    assert np.array_equal(np.array(end.rx.offs, np.uint64), offs) and np.array_equal(np.array(end.rx.lens, np.uint32), lens)
     crc = torch.zeros(1, dtype=torch.int32, device="cuda")
-    W.crc32_buffer(end.whole[64:], total, crc)
-    assert int(_u32(crc)[0]) == O.crc32(host)
-    assert all(t.numel() == M.STREAM_WINDOW for t in end.acked + end.sent + end.sl)
-    assert W.device_status(0, clear=False) & DATA_ERROR_BITS == 0
+    W.crc32_buffer(end.rx.whole.t, total, crc)
+    assert int(u32(crc)[0]) == O.crc32(host)
+    assert all(t.numel() == M.STREAM_WINDOW for t in end.acked + end.sent + end.rx.sl)
+    assert_no_data_error(W)
