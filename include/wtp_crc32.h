@@ -205,7 +205,12 @@ int wtp_build_data_packets_var(const void *d_base, size_t base_bytes,
    the file image from chunk seq0 on (slot s = bytes [s*1456, (s+1)*1456)), and
    d_slot_len[window], WTP_SLOT_EMPTY for an empty slot, else the payload length stored
    in it (set it to 0xFF bytes once; shift or reset it when the window advances:
-   wtp_rx_advance below does that on the device).
+   wtp_rx_advance below does that on the device).  On entry every d_slot_len value must be
+   WTP_SLOT_EMPTY or below 0x80000000: any such value other than WTP_SLOT_EMPTY counts as
+   filled (for placing and for the ACK alike) and is carried unchanged, whether or not it
+   is a possible payload length.  Values in [0x80000000, 0xFFFFFFFF) are the call's own
+   transient claims (0x80000000 | datagram index) and are not valid input: a datagram may
+   be placed over one.  A completed call leaves none behind.
    The result equals processing the datagrams one by one in index (arrival) order:
    d_ok[i] is what wtp_crc32_verify_batch writes.  Datagram i is placed iff d_ok[i],
    ntohl(type) == WTP_TYPE_DATA, len = recv_len - 16 <= WTP_MAX_PAYLOAD,
@@ -218,8 +223,11 @@ int wtp_build_data_packets_var(const void *d_base, size_t base_bytes,
    stay as they were; a slot never mixes two datagrams' bytes.  *d_ack = seq0 + the number
    of leading non-empty slots after the call (the cumulative ACK).  d_place and d_ack may
    be NULL.  n == 0 and window == 0 are valid; with n == 0, *d_ack is still written from
-   the existing state.  n < 2^31.  Fast copy (16-B vectors): a 16-B aligned ring with
-   stride % 16 == 0 and a 16-B aligned d_out; other alignments are copied bytewise.
+   the existing state.  WTP_EINVAL (before any device is touched): a NULL d_dgrams,
+   d_recv_len, d_ok, d_out or d_slot_len with n > 0, stride < 16, n >= 2^31.  Fast copy
+   (16-B vectors), chosen per datagram: a payload whose address in the ring and whose slot
+   in d_out are both 16-B aligned (every datagram of a 16-B aligned ring with stride % 16
+   == 0 and a 16-B aligned d_out); any other datagram is copied bytewise.
    Stream-ordered launches (verify, claim, place) with no host synchronisation; the call
    uses no memory besides the caller's buffers (slots are claimed in d_slot_len itself)
    and keeps no state: graph captures, replays and concurrent calls on different windows

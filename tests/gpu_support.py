@@ -1,11 +1,12 @@
 """What the protocol GPU tests (tests/test_gpu_<call>.py) share: the library fixtures, the
 u32 conversions, guarded device buffers, the first-mismatch reporter, the graph capture and
-replay choreography, the record batch of the mixed-length calls, and the device endpoints
-behind the model loops.  Nothing here is about one call; a new call's test file takes these
+replay choreography, the record batch of the mixed-length calls, the guarded receive window
+and the device endpoints behind the model loops.  Nothing here is about one call; a new call's test file takes these
 from here and defines none of its own."""
 import numpy as np
 import pytest
 
+import accept_model
 import buildvar_model
 import oracle as O
 import retx_model as R
@@ -210,6 +211,64 @@ def datagram_ring(dgrams, stride, salt=0):
         ring[i * stride:i * stride + cut] = np.frombuffer(d[:cut], dtype=np.uint8)
         rl[i] = len(d)
     return ring, rl
+
+
+# ---- the receive window ---------------------------------------------------------------------
+class DevWindow:
+    """The caller-owned state of wtp_accept_data_packets on the device and its host copy: a
+    0xA5 image of `window` slots at byte `out_off` past a 16-B aligned address, between 64
+    guard bytes, and slot_len (EMPTY, or the values of `slot_len`) with guard words.  stage()
+    uploads one batch (the ring at byte `ring_off` between guards, recv_len) and sentinel-filled
+    outputs; check() compares all five outputs with the model's, every guard, and the ring and
+    recv_len with what was uploaded; accept() is stage, the call, the model from the same entry
+    state, check, and the carry-over of the state."""
+    OK_SENT, PLACE_SENT, ACK_SENT = 7, 12345, 0x0BADACC0
+
+    def __init__(self, window, out_off=0, slot_len=None, device="cuda"):
+        self.window, self.device = window, device
+        self.h_out = np.full(window * MAXP, 0xA5, dtype=np.uint8)
+        self.h_slot_len = (np.full(window, accept_model.EMPTY, dtype=np.uint32) if slot_len is None
+                           else np.array(slot_len, dtype=np.uint32))
+        assert self.h_slot_len.size == window
+        self.img = Bytes(self.h_out, off=out_off, front=64, back=64, device=device)
+        self.sl = Words(self.h_slot_len, device=device)
+        self.out, self.slot_len = self.img.t, self.sl.t
+
+    def stage(self, ring, recv_len, ring_off=0):
+        self.ring = Bytes(ring, off=ring_off, front=64, back=64, device=self.device)
+        self.rl_host = np.array(recv_len, dtype=np.uint32)
+        self.rl = Words(self.rl_host, device=self.device)
+        n = self.n = self.rl.n
+        self.ok = Bytes(fill=self.OK_SENT, size=n, front=16, back=16, device=self.device)
+        self.place = Words(self.PLACE_SENT, n, device=self.device)
+        self.ack = Words(self.ACK_SENT, 1, device=self.device)
+
+    def check(self, want, with_place=True, with_ack=True):
+        """`want`: accept_model.accept's (ok, place, out, slot_len, ack).  An output that was
+        not given to the call still holds its sentinel."""
+        want_ok, want_place, want_out, want_sl, want_ack = want
+        n = self.n
+        assert np.array_equal(self.ok.get(), want_ok)
+        assert np.array_equal(self.place.get(), want_place if with_place else np.full(n, self.PLACE_SENT, np.uint32))
+        assert np.array_equal(self.sl.get(), want_sl)
+        assert_bytes_equal(self.img.get(), want_out, MAXP, lambda s: f"image slot {s}, slot_len {want_sl[s]:#x}")
+        assert int(self.ack.get()[0]) == (want_ack if with_ack else self.ACK_SENT)
+        assert np.array_equal(self.ring.get(), self.ring.host)  # the inputs are only read
+        assert np.array_equal(self.rl.get(), self.rl_host)
+
+    def accept(self, W, ring, stride, recv_len, seq0, ring_off=0, with_place=True, with_ack=True):
+        """One call on the device and in the model; returns the model's (ok, place, ack)."""
+        self.stage(ring, recv_len, ring_off)
+        W.accept_data_packets(self.ring.t, stride, self.rl.t, self.n, seq0, self.window, self.out, self.slot_len,
+                              self.ok.t, self.place.t if with_place else None, self.ack.t if with_ack else None)
+        torch.cuda.synchronize()
+        want = accept_model.accept(ring, stride, recv_len, seq0, self.window, self.h_out, self.h_slot_len)
+        self.check(want, with_place, with_ack)
+        if self.n or with_ack:  # n == 0 without d_ack launches nothing
+            assert W.LIB.wtp_last_kernel().decode() == "k_accept_place"
+        assert_no_data_error(W)
+        self.h_out, self.h_slot_len = want[2], want[3]
+        return want[0], want[1], want[4]
 
 
 # ---- device endpoints -------------------------------------------------------------------------

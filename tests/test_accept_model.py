@@ -89,6 +89,62 @@ def test_model_window_wrap_types_and_lengths():
     assert (place == M.NOT_PLACED).all() and ack == seq0
 
 
+def test_fuzz_corpus_is_not_vacuous():
+    """The corpus of test_gpu_accept.py's test_fuzz_against_the_model, judged by the model
+    alone: every batch of 8 or more datagrams carries every kind its stride permits; per seed,
+    over its three calls, every kind has a datagram made for that kind alone on which the
+    model's verdict is the one the kind stands for; the seeds cover every stride and offset,
+    a window across the 2^32 wrap, n == 0 and n == 8; at least 3 seeds copy every payload with
+    16-B vectors, 3 none and 2 some of each batch; and in at least 8 of the 12 seeds the final
+    ACK lies strictly inside the window."""
+    inside, seen_n, shapes, wraps, copies = 0, set(), set(), 0, []
+    for seed in M.FUZZ_SEEDS:
+        rng, window, seq0, stride, ring_off, out_off, ns = M.fuzz_case(seed)
+        assert 1 <= window <= 700 and stride in M.FUZZ_STRIDES and len(ns) == 3
+        assert seq0 >= 0xFFFFFD00 if seed % 2 else 0 <= seq0 < 1 << 32
+        shapes |= {("stride", stride), ("ring", ring_off), ("out", out_off)}
+        # which datagrams take the 16-B vector copy (the buffers are 16-B aligned before their offsets)
+        vec = {(ring_off + i * stride) % 16 == 0 and out_off == 0 for i in range(8)}
+        copies.append("all" if vec == {True} else "none" if vec == {False} else "mixed")
+        wraps += seq0 + window > 1 << 32
+        out, sl = _state(window)
+        shown = set()
+        for n in ns:
+            ring, rl, kinds = M.fuzz_batch(rng, seq0, window, stride, sl, n)
+            assert rl.size == n and ring.size == n * stride and (n == 0 or 8 <= n <= 600)
+            seen_n.add(n)
+            if n:
+                assert set().union(*kinds) == set(M.fuzz_kinds(stride))
+            ok, place, out, sl, ack = M.accept(ring, stride, rl, seq0, window, out, sl)
+            for i, k in enumerate(kinds):
+                if len(k) == 1:
+                    placed = place[i] != M.NOT_PLACED
+                    kind = next(iter(k))
+                    if M.fuzz_verdict(kind, bool(ok[i]), placed, int(rl[i]), int(sl[place[i]]) if placed else None):
+                        shown.add(kind)
+        assert shown == set(M.fuzz_kinds(stride)), (seed, set(M.fuzz_kinds(stride)) - shown)
+        inside += 0 < ((ack - seq0) & M.M32) < window
+    assert inside >= 8
+    assert 0 in seen_n and 8 in seen_n
+    assert shapes == {("stride", s) for s in M.FUZZ_STRIDES} | {("ring", 0), ("ring", 1), ("ring", 8), ("out", 0), ("out", 4)}
+    assert wraps >= 1
+    assert copies.count("all") >= 3 and copies.count("mixed") >= 2 and copies.count("none") >= 3
+
+
+def test_fuzz_batch_deals_every_kind_to_a_small_batch():
+    """n == 8: the 17 kinds share 8 datagrams, no datagram holds two kinds of one group, and
+    the in-batch duplicate follows its original with the same seqNum and another length."""
+    rng = np.random.default_rng(1)
+    ring, rl, kinds = M.fuzz_batch(rng, 100, 50, 1504, np.full(50, M.EMPTY, np.uint32), 8)
+    assert set().union(*kinds) == set(M.FUZZ_KINDS)
+    groups = [set(M.FUZZ_KINDS[:7]), set(M.FUZZ_KINDS[7:11]), set(M.FUZZ_KINDS[11:15]), set(M.FUZZ_KINDS[15:])]
+    assert all(len(k & g) <= 1 for k in kinds for g in groups)
+    first = next(i for i, k in enumerate(kinds) if "placeable" in k)
+    dup = next(i for i, k in enumerate(kinds) if "dup_batch" in k)
+    assert first < dup and ring[first * 1504 + 4:first * 1504 + 8].tobytes() == ring[dup * 1504 + 4:dup * 1504 + 8].tobytes()
+    assert ring[first * 1504 + 8:first * 1504 + 12].tobytes() != ring[dup * 1504 + 8:dup * 1504 + 12].tobytes()  # length
+
+
 def test_accept_argument_validation_without_device():
     import wtp_crc32 as W
     L = W.LIB

@@ -4,7 +4,9 @@ reporter naming the right place.  The buffers live on the CPU device, so no GPU 
 import numpy as np
 import pytest
 
-from gpu_support import Bytes, Words, assert_bytes_equal
+import accept_model
+import oracle as O
+from gpu_support import Bytes, DevWindow, Words, assert_bytes_equal, datagram_ring, s32, torch
 
 
 @pytest.mark.parametrize("dtype", [np.uint32, np.uint64])
@@ -61,6 +63,52 @@ def test_bytes_filled_with_the_guard_or_another_byte():
     assert ring.buf.numel() == 64 + 1 + 48 + 64 and (ring.get() == 0xA5).all()
     img = Bytes(fill=0x3C, size=48, guard=0xC3, device="cpu")
     assert (img.get() == 0x3C).all() and (img.buf[48:] == 0xC3).all()
+
+
+def test_dev_window_checks_every_output_guard_and_input():
+    """DevWindow.check on the CPU device, with the model's own result written into the staged
+    buffers in place of the call: it passes, it passes with an output withheld only if that
+    output still holds its sentinel, and it fails for one wrong element of each output, one
+    changed byte in front of or behind the image, behind ok, place, ack or slot_len, and one
+    changed byte of the ring or of recv_len."""
+    dg = [O.build_datagram(s, bytes([s]) * (100 + s)) for s in (2, 0, 2, 9)]
+    ring, rl = datagram_ring(dg, 1472)
+    want = accept_model.accept(ring, 1472, rl, 0, 4, np.full(4 * 1456, 0xA5, np.uint8), np.full(4, accept_model.EMPTY, np.uint32))
+    assert want[1].tolist() == [2, 0, accept_model.NOT_PLACED, accept_model.NOT_PLACED] and want[4] == 1
+
+    def staged(with_place=True, with_ack=True):
+        win = DevWindow(4, out_off=4, device="cpu")
+        assert win.out.data_ptr() % 16 == 4 and win.slot_len.numel() == 4
+        win.stage(ring, rl, ring_off=1)
+        assert win.ring.t.data_ptr() % 16 == 1
+        win.ok.payload.copy_(torch.from_numpy(want[0]))
+        if with_place:
+            win.place.t.copy_(torch.from_numpy(s32(want[1])))
+        win.img.payload.copy_(torch.from_numpy(want[2]))
+        win.slot_len.copy_(torch.from_numpy(s32(want[3])))
+        if with_ack:
+            win.ack.t[0] = want[4]
+        return win
+
+    staged().check(want)
+    staged(with_place=False).check(want, with_place=False)
+    staged(with_ack=False).check(want, with_ack=False)
+    spoil = [lambda w: w.ok.payload[3].fill_(0), lambda w: w.place.t[2].fill_(2), lambda w: w.slot_len[1].fill_(0),
+             lambda w: w.img.payload[2 * 1456 + 102].fill_(2), lambda w: w.ack.t[0].fill_(2),
+             lambda w: w.img.buf[w.img.lo - 1].fill_(0), lambda w: w.img.payload[4 * 1456 - 1].fill_(0),
+             lambda w: w.img.t[4 * 1456].fill_(0), lambda w: w.ok.t[4].fill_(0), lambda w: w.ok.buf[15].fill_(0),
+             lambda w: w.place.buf[4].fill_(0), lambda w: w.ack.buf[1].fill_(0), lambda w: w.sl.buf[4].fill_(0),
+             lambda w: w.ring.payload[1472 * 3 + 1471].fill_(0x11), lambda w: w.ring.t[4 * 1472].fill_(0),
+             lambda w: w.rl.t[3].fill_(16), lambda w: w.rl.buf[4].fill_(0)]
+    for k, f in enumerate(spoil):
+        win = staged()
+        f(win)
+        with pytest.raises(AssertionError):
+            win.check(want)
+            pytest.fail(f"spoiler {k} went unnoticed")
+    for kw in (dict(with_place=False), dict(with_ack=False)):  # a withheld output that was written after all
+        with pytest.raises(AssertionError):
+            staged().check(want, **kw)
 
 
 def test_mismatch_reporter():
