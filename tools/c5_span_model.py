@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where k_pieces' extra HBM reads on C5 come from: a CPU model of the launch's read
-REQUESTS (not its CRCs).  Mirrors csrc/crc32_kernels.hip k_pieces + WaveSplit +
+REQUESTS (not its CRCs).  Mirrors csrc/crc32_pieces.hpp k_pieces + WaveSplit +
 pieces_loop: 256 workgroups x 16 waves, wave ranges balanced by pieces, the round cut
 at the first window outside the slot span, the speculative span prefetch (hit / miss
 reload) and the per-round metadata loads.  Counts, per launch, the 128-B lines each

@@ -4,7 +4,7 @@
 Build it only if this predicts <= 38 us from a graph (frac >= 0.51) for C5 (1 M packed
 Zipf(1.1) payloads, 142.1 MB + 12 B metadata each = 154.7 MB read).
 
-Per-round operation counts come from the shipped source (csrc/crc32_kernels.hip k_stream,
+Per-round operation counts come from the shipped source (csrc/crc32_stream.hpp k_stream,
 stag_apply3x = 4 v_perm + 4 ds_read_b32 + 2 v_xor3; nib_apply = 8 v_bfe + 8 address
 adds + 8 ds_read_b32 + 4 xor; one dependent LDS round trip per apply).  Three limits per
 design, each calibrated on a kernel measured on the same part:
