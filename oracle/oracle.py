@@ -2,7 +2,8 @@
 
 Loads oracle/liboracle.so (the from-scratch restatement, crc32_oracle.c) and, when
 present, oracle/_ref/libref_crc32.so (the reference's own cpp/src/common/Crc32.hpp
-compiled in this container).  Only tests/, __graft_entry__.smoke() and bench.py's
+compiled in this container) and oracle/_ref/libref_packet_{base,opt}.so (its Packet and
+Window code, through ref_packet_shim.cpp).  Only tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg import this module; the product path never does.
 """
 from __future__ import annotations
@@ -79,6 +80,67 @@ def ref_lib() -> C.CDLL | None:
         r.ref_crc32_batch_fixed_mt.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, _u32p, C.c_int]
         _REF = r
     return _REF
+
+
+_REF_PACKET: dict[str, C.CDLL] = {}
+
+
+def ref_packet_lib(variant: str) -> C.CDLL | None:
+    """The reference's compiled Packet code, `variant` "base" or "opt" (oracle/_ref/
+    libref_packet_<variant>.so, through ref_packet_shim.cpp), or None when it was not built.
+    The opt library also holds the reference's Window (ref_window_run)."""
+    if variant not in ("base", "opt"):
+        raise ValueError(f"unknown variant {variant!r}")
+    path = os.path.join(HERE, "_ref", f"libref_packet_{variant}.so")
+    if variant not in _REF_PACKET and os.path.exists(path):
+        r = C.CDLL(path)
+        r.ref_packet_build.restype = None
+        r.ref_packet_build.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, _u8p]
+        r.ref_packet_parse.restype = C.c_int
+        r.ref_packet_parse.argtypes = [C.c_void_p, C.c_size_t, _u32p]
+        if variant == "opt":
+            r.ref_window_run.restype = C.c_size_t
+            r.ref_window_run.argtypes = [C.c_int, C.c_uint32, C.c_uint32, _u32p, C.c_size_t, _u8p]
+        _REF_PACKET[variant] = r
+    return _REF_PACKET.get(variant)
+
+
+def ref_build_datagram(r: C.CDLL, ptype: int, seq: int, payload: bytes) -> bytes:
+    """The reference's Packet(ptype, payload, seq) as its sender serialises it."""
+    p = np.frombuffer(bytes(payload), dtype=np.uint8)
+    out = np.zeros(16 + p.size, dtype=np.uint8)
+    r.ref_packet_build(ptype, _ptr(p) if p.size else None, p.size, seq, _ptr(out, _u8p))
+    return out.tobytes()
+
+
+def ref_parse_datagram(r: C.CDLL, dgram: bytes):
+    """The reference's Packet(buf, size): [type, seqNum, length, checksum, calculateCheckSum()],
+    the last over header.length bytes (zero-padded past the datagram's end, see the shim)."""
+    b = np.frombuffer(bytes(dgram), dtype=np.uint8)
+    out = np.zeros(5, dtype=np.uint32)
+    if r.ref_packet_parse(_ptr(b), b.size, _ptr(out, _u32p)) != 0:
+        raise ValueError("the shim refuses this datagram (shorter than a header, or a length field above 65536)")
+    return [int(v) for v in out]
+
+
+def ref_window_run(r: C.CDLL, seq0: int, inflight: int, acks):
+    """The reference's opt Window holding seq0 .. seq0 + inflight - 1, fed markPacketAsAcked
+    for each seqNum of `acks` in order: (acked flags, determineWindowAdvance()).  The
+    reference prints a line per mark, so file descriptors 1 and 2 are silenced around the call."""
+    a = np.ascontiguousarray(acks, dtype=np.uint32)
+    flags = np.zeros(inflight, dtype=np.uint8)
+    saved = [os.dup(fd) for fd in (1, 2)]
+    null = os.open(os.devnull, os.O_WRONLY)
+    try:
+        for fd in (1, 2):
+            os.dup2(null, fd)
+        adv = int(r.ref_window_run(max(inflight, 1), seq0, inflight, _ptr(a, _u32p), a.size, _ptr(flags, _u8p)))
+    finally:
+        for fd, keep in zip((1, 2), saved):
+            os.dup2(keep, fd)
+            os.close(keep)
+        os.close(null)
+    return flags, adv
 
 
 # ---- convenience wrappers ---------------------------------------------------------
