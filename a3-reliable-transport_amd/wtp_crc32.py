@@ -28,6 +28,8 @@ RETX_ALL = 1                  # WTP_RETX_ALL: flags of tx_build_retransmit
 TX_MAX_INFLIGHT = 1 << 20     # WTP_TX_MAX_INFLIGHT
 RX_MAX_WINDOW = 1 << 20       # WTP_RX_MAX_WINDOW (cumulative mode of rx_build_acks)
 RX_MAX_BATCH = 1 << 24        # WTP_RX_MAX_BATCH
+RX_MAX_FLOWS = 1 << 20        # WTP_RX_MAX_FLOWS
+RX_MAX_FLOW_SLOTS = 1 << 24   # WTP_RX_MAX_FLOW_SLOTS (nflows * window of accept_data_packets_flows)
 
 
 class WtpError(RuntimeError):
@@ -63,6 +65,10 @@ def _load() -> C.CDLL:
                                               sz, vp]),
         "wtp_rx_ack_work_bytes": (sz, [sz, u32, u32]),
         "wtp_rx_build_acks": (i32, [vp, sz, vp, sz, u32, u32, u32, vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, sz, vp]),
+        "wtp_accept_data_packets_flows": (i32, [vp, sz, vp, vp, sz, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "wtp_rx_ack_flows_work_bytes": (sz, [sz]),
+        "wtp_rx_build_acks_flows": (i32, [vp, sz, vp, vp, sz, u32, vp, u32, u32, vp, vp, vp, sz, u32, u32, vp, vp, vp, sz,
+                                          vp]),
         "wtp_rx_deliver_work_bytes": (sz, [u32]),
         "wtp_rx_deliver": (i32, [vp, vp, u32, u32, vp, sz, u64, vp, vp, vp, vp, sz, vp]),
         "wtp_rx_advance": (i32, [vp, vp, u32, vp, vp, vp, vp]),
@@ -95,6 +101,7 @@ EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_coun
             "wtp_build_data_packets_var", "wtp_accept_data_packets", "wtp_tx_ingest_acks", "wtp_tx_work_bytes", "wtp_tx_build_retransmit",
             "wtp_tx_build_retransmit_var", "wtp_rx_ack_work_bytes", "wtp_rx_build_acks", "wtp_rx_deliver_work_bytes", "wtp_rx_deliver",
             "wtp_rx_advance", "wtp_tx_advance",
+            "wtp_accept_data_packets_flows", "wtp_rx_ack_flows_work_bytes", "wtp_rx_build_acks_flows",
             "wtp_crc32_combine", "wtp_crc32_concat_work_bytes", "wtp_crc32_concat", "wtp_crc32_buffer_work_bytes",
             "wtp_crc32_buffer", "wtp_crc32_host_buffer",
             "wtp_crc32_host_batch_fixed", "wtp_crc32_host_chunked", "wtp_crc32_host_chunked_multi", "wtp_crc32_host_verify",
@@ -241,6 +248,39 @@ def rx_build_acks(dgrams, stride: int, recv_len, n: int, mode: int, seq0: int, w
     _check(LIB.wtp_rx_build_acks(_dptr(dgrams), stride, _dptr(recv_len), n, mode, seq0 & 0xFFFFFFFF, window, _dptr(ok),
                                  _dptr(place), _dptr(slot_len), _dptr(ack_wire), ack_stride, skip, max_acks,
                                  _dptr(src), _dptr(counts), wp, wb, _stream(stream)), "wtp_rx_build_acks")
+
+
+# ---- multi-connection receive ------------------------------------------------------------
+def accept_data_packets_flows(dgrams, stride: int, recv_len, flow, n: int, seq0, nflows: int, window: int, out,
+                              slot_len, ok, place=None, ack=None, stream=None) -> None:
+    """accept_data_packets for the interleaved arrivals of many connections
+    (wtp_accept_data_packets_flows): `flow` (n x u32) names each datagram's connection (>=
+    nflows: none), `seq0` (nflows x u32, device) each connection's window base.  Flow f owns
+    slots [f*window, (f+1)*window) of `out` (nflows * window * 1456 B) and `slot_len`;
+    `place` (n x u32) is the slot within the flow, `ack` (nflows x u32) each flow's
+    cumulative ACK."""
+    _check(LIB.wtp_accept_data_packets_flows(_dptr(dgrams), stride, _dptr(recv_len), _dptr(flow), n, _dptr(seq0), nflows,
+                                             window, _dptr(out), _dptr(slot_len), _dptr(ok), _dptr(place), _dptr(ack),
+                                             _stream(stream)), "wtp_accept_data_packets_flows")
+
+
+def rx_ack_flows_work_bytes(n: int) -> int:
+    return int(LIB.wtp_rx_ack_flows_work_bytes(n))
+
+
+def rx_build_acks_flows(dgrams, stride: int, recv_len, flow, n: int, mode: int, seq0, nflows: int, window: int, ok,
+                        flow_ack, ack_wire, ack_stride: int, skip: int, max_acks: int, src=None, counts=None, work=None,
+                        stream=None) -> None:
+    """The ACK datagrams a receiver owes for a batch that accept_data_packets_flows has
+    processed (wtp_rx_build_acks_flows): `ok` is accept's output and `flow_ack` its per-flow
+    `ack` (the seqNum of every cumulative ACK of that flow; unused and may be None with
+    ACK_SELECTIVE).  The eligible datagrams of rank [skip, skip + max_acks) become 16-byte
+    ACKs in `ack_wire` with their datagram index in `src` (the reply goes to the address of
+    flow[src[k]]); counts (2 x u32) = (emitted, eligible)."""
+    work, wp, wb = _work(work, rx_ack_flows_work_bytes(n))
+    _check(LIB.wtp_rx_build_acks_flows(_dptr(dgrams), stride, _dptr(recv_len), _dptr(flow), n, mode, _dptr(seq0), nflows,
+                                       window, _dptr(ok), _dptr(flow_ack), _dptr(ack_wire), ack_stride, skip, max_acks,
+                                       _dptr(src), _dptr(counts), wp, wb, _stream(stream)), "wtp_rx_build_acks_flows")
 
 
 # ---- in-order flush of the window ------------------------------------------------------

@@ -441,6 +441,101 @@ int wtp_rx_build_acks(const void *d_dgrams, size_t stride, const uint32_t *d_rec
                       uint32_t *d_src, uint32_t *d_counts,
                       void *d_work, size_t work_bytes, void *stream);
 
+/* ---- multi-connection receive: accept and ACK one batch across flows ------------------
+   wtp_accept_data_packets and wtp_rx_build_acks for a receiver with many concurrent
+   senders: one batch holds the arrivals of all connections, interleaved in arrival order
+   (what recvmmsg returns), and one call serves every connection's window.  Per-connection
+   semantics are exactly those of the two calls above (the reference serves one connection
+   at a time and drops a second START, cpp/src/opt/Receiver.cpp:145-150); only the
+   batching across connections is new.
+
+   State.  All flows share one `window`, the receiver's parameter.  Flow f in [0, nflows)
+   owns slots [f*window, (f+1)*window) of one d_slot_len[nflows*window] and one image d_out
+   of nflows*window*1456 bytes: its sub-window is d_out + f*window*1456, d_slot_len +
+   f*window, which is the state wtp_accept_data_packets, wtp_rx_deliver and wtp_rx_advance
+   take, so the per-flow flush and slide use those calls unchanged.  d_seq0[nflows] (device
+   memory, read when the kernels run) is each flow's window base: the host or a device step
+   updates it between rounds, and one captured graph serves every round.  d_flow[n] (device)
+   names each datagram's flow, derived by the caller from the datagram's source address;
+   any value >= nflows means "no connection".
+
+   wtp_accept_data_packets_flows.  The result equals processing the datagrams one by one in
+   index (arrival) order, each against its own flow's window; equivalently, for every flow
+   f it is what wtp_accept_data_packets gives on the subsequence of datagrams with d_flow[i]
+   == f, in index order, against flow f's sub-window with seq0 = d_seq0[f].  d_ok[i] is what
+   wtp_crc32_verify_batch writes, for every datagram ("no connection" ones included).
+   Datagram i is placed iff d_ok[i], f = d_flow[i] < nflows, ntohl(type) == WTP_TYPE_DATA,
+   len = recv_len - 16 <= WTP_MAX_PAYLOAD, s = ntohl(seqNum) - d_seq0[f] (unsigned 32-bit, so
+   a wrapping window is well defined) < window, slot f*window + s was empty on entry and no
+   placed datagram of a lower index and the same flow carries the same seqNum (first arrival
+   wins).  Then d_out[(f*window + s)*1456 .. +len) = payload, d_slot_len[f*window + s] = len
+   and d_place[i] = s, the slot within the flow (so nflows == 1 reproduces
+   wtp_accept_data_packets word for word); otherwise d_place[i] = WTP_NOT_PLACED.  The same
+   seqNum in two flows never collides.  d_ack[f] = d_seq0[f] + the number of leading
+   non-empty slots of flow f after the call, written for every f < nflows, also with n == 0
+   and for a flow that no datagram names.  As in wtp_accept_data_packets: on entry every
+   d_slot_len value is WTP_SLOT_EMPTY or below 0x80000000, values in [0x80000000, 0xFFFFFFFF)
+   are the call's transient claims (0x80000000 | datagram index) and a completed call leaves
+   none behind; nothing else in d_out or d_slot_len changes; a slot never mixes two
+   datagrams' bytes; the inputs are only read; the copy is 16-B vectors for a datagram
+   whose payload address and slot are both 16-B aligned, bytes otherwise (1456 = 91 * 16, so
+   a 16-B aligned d_out keeps every flow's slots aligned).  d_place and d_ack may be NULL.
+   n == 0, nflows == 0 and window == 0 are valid.
+   WTP_EINVAL (before any device is touched, each with its own message): n >= 2^31, stride <
+   16, nflows > WTP_RX_MAX_FLOWS, window > WTP_RX_MAX_WINDOW, nflows * window (in 64 bits) >
+   WTP_RX_MAX_FLOW_SLOTS, a NULL d_dgrams, d_recv_len, d_flow, d_ok, d_out or d_slot_len with
+   n > 0, a NULL d_seq0 with nflows > 0 and (n > 0 or d_ack).
+   Stream-ordered launches (verify, claim, place + per-flow ACK) with no host
+   synchronisation; no memory besides the caller's buffers (claims live in d_slot_len) and
+   no library state: graph captures, replays and concurrent calls on different states are
+   independent.  The per-flow ACK costs no launch and no serial walk per flow: all
+   nflows*window slots are spread over the place kernel's grid, 2^20 flows of 16 slots and
+   one flow of 2^20 slots alike.  wtp_last_kernel() names "k_flows_place".
+
+   wtp_rx_build_acks_flows follows it on the same stream with the same batch, d_flow, d_seq0
+   values, nflows and window, accept's d_ok and (in cumulative mode) its d_ack as d_flow_ack.
+   Eligibility is wtp_rx_build_acks' rule with the flow's base: datagram i is answered iff
+   d_ok[i] != 0, f = d_flow[i] < nflows, ntohl(type) == WTP_TYPE_DATA, recv_len[i] - 16 <=
+   WTP_MAX_PAYLOAD and, with d = ntohl(seqNum) - d_seq0[f], d < window or d >= 0x80000000.
+   The ACK's seqNum: WTP_ACK_SELECTIVE, the datagram's own seqNum (d_flow_ack is not read
+   and may be NULL); WTP_ACK_CUMULATIVE, d_flow_ack[f], the flow's cumulative ACK after the
+   whole batch.  This differs from wtp_rx_build_acks, which gives the running value after
+   each arrival: a cumulative ACK that names a later next-expected packet is always valid,
+   and the sender's wtp_tx_ingest_acks takes the batch maximum anyway; the running value
+   across flows is a segmented prefix problem and is not computed here.
+   Output as in wtp_rx_build_acks: the eligible datagrams are ranked in arrival order, those
+   of rank r in [skip, skip + max_acks) become entry k = r - skip of d_ack_wire (16 bytes,
+   ack_stride apart) with d_src[k] = i (the reply address is that of d_flow[d_src[k]]);
+   d_counts = {emitted, eligible}; entries past d_counts[0], bytes [16, ack_stride) of every
+   slot and every input stay as they were; d_src may be NULL; one 16-B store per 16-B
+   aligned slot, bytes otherwise.  n == 0, nflows == 0, window == 0 and max_acks == 0 are
+   valid: d_counts is still written.  d_work is scratch as in wtp_rx_build_acks (any
+   alignment); wtp_rx_ack_flows_work_bytes is monotone in n and at most 64 KiB + 4 bytes per
+   1024 datagrams.
+   WTP_EINVAL (before any device is touched): n > WTP_RX_MAX_BATCH, an unknown mode, window >
+   WTP_RX_MAX_WINDOW in cumulative mode, stride < 16, ack_stride < 16, work_bytes <
+   wtp_rx_ack_flows_work_bytes(n), a NULL d_counts or d_work; with n > 0, a NULL d_dgrams,
+   d_recv_len, d_ok or d_flow, a NULL d_seq0 with nflows > 0, a NULL d_flow_ack in cumulative
+   mode with nflows > 0, a NULL d_ack_wire with max_acks > 0.
+   Stream-ordered launches (mark, emit), no host synchronisation, no state, no library
+   table: no wtp_init is needed before a capture.  wtp_last_kernel() names
+   "k_flows_ack_emit". */
+#define WTP_RX_MAX_FLOWS      (1u << 20)
+#define WTP_RX_MAX_FLOW_SLOTS (1u << 24)   /* nflows * window */
+int wtp_accept_data_packets_flows(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len,
+                                  const uint32_t *d_flow, size_t n,
+                                  const uint32_t *d_seq0, uint32_t nflows, uint32_t window,
+                                  void *d_out, uint32_t *d_slot_len,
+                                  uint8_t *d_ok, uint32_t *d_place, uint32_t *d_ack, void *stream);
+size_t wtp_rx_ack_flows_work_bytes(size_t n);
+int wtp_rx_build_acks_flows(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len,
+                            const uint32_t *d_flow, size_t n, uint32_t mode,
+                            const uint32_t *d_seq0, uint32_t nflows, uint32_t window,
+                            const uint8_t *d_ok, const uint32_t *d_flow_ack,
+                            void *d_ack_wire, size_t ack_stride, uint32_t skip, uint32_t max_acks,
+                            uint32_t *d_src, uint32_t *d_counts,
+                            void *d_work, size_t work_bytes, void *stream);
+
 /* ---- in-order flush: the window's leading run as a packed stream ---------------------
    The sixth call of the protocol loop (cpp/src/base/Receiver.cpp:208-237, the in-order
    flush; wReceiver.cpp's std::map loop): it follows wtp_accept_data_packets and
