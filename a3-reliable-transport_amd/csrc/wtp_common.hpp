@@ -1,5 +1,5 @@
 // wtp_common.hpp — what the protocol translation units (wtp_accept.hip, wtp_concat.hip,
-// wtp_tx.hip, wtp_txvar.hip, wtp_ack.hip, wtp_buildvar.hip, wtp_deliver.hip, wtp_advance.hip, wtp_flows.hip) share: error plumbing and argument checks on the host, and on
+// wtp_tx.hip, wtp_txvar.hip, wtp_ack.hip, wtp_buildvar.hip, wtp_deliver.hip, wtp_advance.hip, wtp_flows.hip, wtp_flows_flush.hip) share: error plumbing and argument checks on the host, and on
 // the device the header's wire format and the wave reductions.
 // Internal: the C-ABI is include/wtp_crc32.h.
 //

@@ -73,6 +73,9 @@ def _load() -> C.CDLL:
         "wtp_rx_deliver": (i32, [vp, vp, u32, u32, vp, sz, u64, vp, vp, vp, vp, sz, vp]),
         "wtp_rx_advance": (i32, [vp, vp, u32, vp, vp, vp, vp]),
         "wtp_tx_advance": (i32, [vp, vp, u32, vp, u32, vp, vp, vp]),
+        "wtp_rx_deliver_flows_work_bytes": (sz, [u32, u32]),
+        "wtp_rx_deliver_flows": (i32, [vp, vp, u32, u32, u32, vp, sz, u64, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "wtp_rx_advance_flows": (i32, [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "wtp_crc32_combine": (u32, [u32, u32, u64]),
         "wtp_crc32_concat_work_bytes": (sz, [sz]),
         "wtp_crc32_concat": (i32, [vp, vp, u64, u64, sz, vp, sz, vp, vp]),
@@ -102,6 +105,7 @@ EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_coun
             "wtp_tx_build_retransmit_var", "wtp_rx_ack_work_bytes", "wtp_rx_build_acks", "wtp_rx_deliver_work_bytes", "wtp_rx_deliver",
             "wtp_rx_advance", "wtp_tx_advance",
             "wtp_accept_data_packets_flows", "wtp_rx_ack_flows_work_bytes", "wtp_rx_build_acks_flows",
+            "wtp_rx_deliver_flows_work_bytes", "wtp_rx_deliver_flows", "wtp_rx_advance_flows",
             "wtp_crc32_combine", "wtp_crc32_concat_work_bytes", "wtp_crc32_concat", "wtp_crc32_buffer_work_bytes",
             "wtp_crc32_buffer", "wtp_crc32_host_buffer",
             "wtp_crc32_host_batch_fixed", "wtp_crc32_host_chunked", "wtp_crc32_host_chunked_multi", "wtp_crc32_host_verify",
@@ -317,6 +321,37 @@ def tx_advance(acked, sent_ms, slots: int, adv, fill_ms: int, acked_next, sent_m
     `adv` is a u32 device tensor read when the kernel runs (tx_ingest_acks' counts)."""
     _check(LIB.wtp_tx_advance(_dptr(acked), _dptr(sent_ms), slots, _dptr(adv), fill_ms & 0xFFFFFFFF, _dptr(acked_next),
                               _dptr(sent_ms_next), _stream(stream)), "wtp_tx_advance")
+
+
+# ---- multi-connection flush and slide ----------------------------------------------------
+def rx_deliver_flows_work_bytes(nflows: int, window: int) -> int:
+    return int(LIB.wtp_rx_deliver_flows_work_bytes(nflows, window))
+
+
+def rx_deliver_flows(img, slot_len, nflows: int, window: int, max_slots: int, stream_buf, stream_bytes: int,
+                     stream_off: int, offsets_out, lengths_out, flow_adv, flow_info, counts, work=None, stream=None) -> None:
+    """rx_deliver over every flow of accept_data_packets_flows' state (wtp_rx_deliver_flows): the
+    leading runs of all sub-windows (at most max_slots slots each), flow 0's first, go back to
+    back to `stream_buf` from byte stream_off on as long as whole records fit stream_bytes;
+    offsets_out (u64) / lengths_out (u32) get one packed record list (either may be None),
+    flow_adv (nflows x u64) the slots delivered per flow, flow_info (nflows x 4 x u64, may be
+    None) = (run, first rank, first byte's stream offset, bytes) per flow, counts (4 x u64) =
+    (records, sum of runs, bytes delivered, bytes all runs need)."""
+    work, wp, wb = _work(work, rx_deliver_flows_work_bytes(nflows, window))
+    _check(LIB.wtp_rx_deliver_flows(_dptr(img), _dptr(slot_len), nflows, window, max_slots, _dptr(stream_buf), stream_bytes,
+                                    stream_off, _dptr(offsets_out), _dptr(lengths_out), _dptr(flow_adv), _dptr(flow_info),
+                                    _dptr(counts), wp, wb, _stream(stream)), "wtp_rx_deliver_flows")
+
+
+def rx_advance_flows(img, slot_len, nflows: int, window: int, flow_adv, seq0, img_next, slot_len_next, seq0_next,
+                     stream=None) -> None:
+    """rx_advance for every flow in one launch (wtp_rx_advance_flows): flow f's sub-window moves
+    down by min(flow_adv[f], window) slots (u64 device tensor, rx_deliver_flows' as it is) into
+    `img_next` / `slot_len_next`, and seq0_next[f] = seq0[f] + that (u32 device tensors).  Both
+    images, or both seq0 arrays, may be None."""
+    _check(LIB.wtp_rx_advance_flows(_dptr(img), _dptr(slot_len), nflows, window, _dptr(flow_adv), _dptr(seq0),
+                                    _dptr(img_next), _dptr(slot_len_next), _dptr(seq0_next), _stream(stream)),
+           "wtp_rx_advance_flows")
 
 
 # ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------

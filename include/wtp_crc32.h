@@ -453,9 +453,10 @@ int wtp_rx_build_acks(const void *d_dgrams, size_t stride, const uint32_t *d_rec
    owns slots [f*window, (f+1)*window) of one d_slot_len[nflows*window] and one image d_out
    of nflows*window*1456 bytes: its sub-window is d_out + f*window*1456, d_slot_len +
    f*window, which is the state wtp_accept_data_packets, wtp_rx_deliver and wtp_rx_advance
-   take, so the per-flow flush and slide use those calls unchanged.  d_seq0[nflows] (device
-   memory, read when the kernels run) is each flow's window base: the host or a device step
-   updates it between rounds, and one captured graph serves every round.  d_flow[n] (device)
+   take, so those calls work on one flow unchanged; wtp_rx_deliver_flows and
+   wtp_rx_advance_flows below flush and slide all flows at once.  d_seq0[nflows] (device
+   memory, read when the kernels run) is each flow's window base: wtp_rx_advance_flows (or the
+   host) moves it between rounds, and one captured graph serves every round.  d_flow[n] (device)
    names each datagram's flow, derived by the caller from the datagram's source address;
    any value >= nflows means "no connection".
 
@@ -636,6 +637,104 @@ int wtp_rx_deliver(const void *d_img, const uint32_t *d_slot_len, uint32_t windo
 int wtp_rx_advance(const void *d_img, const uint32_t *d_slot_len, uint32_t window,
                    const uint64_t *d_adv,
                    void *d_img_next, uint32_t *d_slot_len_next, void *stream);
+
+/* ---- multi-connection flush and slide: every flow in one pass -------------------------
+   The second half of the multi-flow receive round: wtp_accept_data_packets_flows ->
+   wtp_rx_build_acks_flows -> wtp_rx_deliver_flows -> wtp_rx_advance_flows, all stream-ordered,
+   with the window bases moved on the device, so one captured graph serves every round of
+   any number of connections with one host read at its end.  The state is accept_flows':
+   flow f owns global slots [f*window, (f+1)*window) of one d_slot_len[nflows*window] and one
+   image of nflows*window*1456 bytes; the limits are WTP_RX_MAX_FLOWS, WTP_RX_MAX_WINDOW and
+   WTP_RX_MAX_FLOW_SLOTS.  Byte sums over the state reach 2^24 * 1456 > 2^32 and are 64-bit.
+
+   wtp_rx_deliver_flows, stated sequentially: run_f = the number of leading slots of flow f's
+   sub-window with d_slot_len <= WTP_MAX_PAYLOAD (wtp_rx_deliver's rule: WTP_SLOT_EMPTY, a
+   claim pattern or any other value ends the run).  The candidates are the slots (f, s) with
+   s < min(run_f, max_slots), in flow-major order (f rising, then s rising); Q_r = the 64-bit
+   sum of the lengths of the candidates before rank r.  K = the largest count such that the
+   first K candidates all have stream_off + Q_r + len_r <= stream_bytes: whole records only
+   and a prefix of the candidate list (the predicate is monotone in r); zero-length records
+   that still fit count.  k_f = the number of flow f's candidates among the first K.
+   Candidate rank r < K, in slot (f, s) with length len, gives d_stream[stream_off + Q_r .. +
+   len) = d_img[(f*window + s)*1456 .. + len), d_offsets_out[r] = stream_off + Q_r and
+   d_lengths_out[r] = len: one packed record list, flow 0's records first, directly usable
+   by wtp_crc32_batch_packed; both arrays hold nflows * min(window, max_slots) entries and
+   may be NULL.  d_flow_adv[f] = k_f, always written
+   for every f < nflows (64-bit: the type of wtp_rx_advance's d_adv).  d_flow_info may be
+   NULL; otherwise d_flow_info[4f .. 4f+4) = {run_f, R_f, B_f, bytes_f}: R_f = the rank of the
+   flow's first delivered record = the sum of k_g over g < f, B_f = the absolute stream offset
+   of its first byte = stream_off + the sum of bytes_g over g < f, bytes_f = the bytes
+   delivered for it; the host routes the ranges [B_f, B_f + bytes_f) of the one stream to the
+   connections.  d_counts[0 .. 4) = {K, the sum of run_f, Q_K, the bytes all runs would need}
+   is always written; the last value ignores max_slots and the capacity, as wtp_rx_deliver's
+   P_run does.
+   Consequences: with nflows == 1 every output equals wtp_rx_deliver's word for word,
+   d_counts included, and d_flow_adv[0] == d_counts[0].  When everything fits, the result
+   equals calling wtp_rx_deliver per flow in order with stream_off moved on by the earlier
+   flows' bytes.  When it does not, the flow where the cut falls delivers a prefix and
+   every later flow delivers nothing, even a record smaller than the room left: its k_f =
+   0, so its window does not move and nothing is lost.
+   Nothing else is written: every byte of d_stream outside [stream_off, stream_off + Q_K)
+   stays as it was, the bytes that share a 16-B vector with the first and last delivered
+   byte included; entries >= K of the record arrays stay as they were; d_img and d_slot_len
+   are only read and no byte outside [d_img, d_img + nflows*window*1456) is loaded.
+   d_stream overlapping d_img is undefined.  nflows == 0, window == 0 and max_slots == 0 are
+   valid: d_counts and d_flow_adv are still written, and with max_slots == 0 the runs are
+   still reported.
+   d_work is the caller's scratch (any alignment, contents arbitrary on entry, unspecified on
+   return; every word the call reads it has written before).  With S = nflows*window and B =
+   ceil(S / 1024), wtp_rx_deliver_flows_work_bytes = 40 + 12*S + 28*B + 16*nflows (its
+   arguments clamped to the limits), monotone in both arguments and at most 64 KiB + 16 bytes
+   per global slot + 16 bytes per flow.
+   WTP_EINVAL (before any device is touched, each with its own message): nflows >
+   WTP_RX_MAX_FLOWS, window > WTP_RX_MAX_WINDOW, nflows*window (in 64 bits) >
+   WTP_RX_MAX_FLOW_SLOTS; stream_off > stream_bytes; work_bytes below the size above; a NULL
+   d_counts or d_work; a NULL d_flow_adv with nflows > 0; a NULL d_img or d_slot_len with
+   nflows*window > 0; a NULL d_stream with nflows*window > 0 and max_slots > 0.
+   Stream-ordered launches (runs, block sums, their scan, the slot scan, the per-flow
+   outputs, the copy) with no host synchronisation, no allocation and no library table, so
+   no wtp_init is needed before a capture; grids are sized from nflows, window and max_slots,
+   never from device values, and nothing is done serially per flow: 2^20 flows of 16 slots
+   and one flow of 2^20 slots are the same work.  Graph captures, replays and concurrent
+   calls on different work buffers are independent.  Fast path as wtp_rx_deliver's (a 4-B
+   aligned d_img; spanning, first, last and edge vectors bytewise, exactly).
+   wtp_last_kernel() names "k_dflows_copy", or the last launch of the scans when nothing can
+   be copied ("k_dflows_out"; "k_dflows_mid" with nflows == 0). */
+size_t wtp_rx_deliver_flows_work_bytes(uint32_t nflows, uint32_t window);
+int wtp_rx_deliver_flows(const void *d_img, const uint32_t *d_slot_len,
+                         uint32_t nflows, uint32_t window, uint32_t max_slots,
+                         void *d_stream, size_t stream_bytes, uint64_t stream_off,
+                         uint64_t *d_offsets_out, uint32_t *d_lengths_out,
+                         uint64_t *d_flow_adv, uint64_t *d_flow_info, uint64_t *d_counts,
+                         void *d_work, size_t work_bytes, void *stream);
+
+/* wtp_rx_advance_flows slides every flow's sub-window and base: wtp_rx_advance per flow, in
+   one launch.  a_f = min(d_flow_adv[f], window), compared in 64 bits and read on the device
+   when the kernel runs, so wtp_rx_deliver_flows' d_flow_adv passes as it is.  For every flow
+   and every s < window, with t = s + a_f and v = d_slot_len[f*window + t] if t < window, else
+   WTP_SLOT_EMPTY: d_slot_len_next[f*window + s] = v, for every v; and if v <= WTP_MAX_PAYLOAD
+   and the images are given, v bytes of slot (f, t) of d_img go to slot (f, s) of d_img_next.
+   Bytes [v, 1456) of a slot and slots that receive nothing stay as they were
+   (wtp_rx_advance's rule, per flow).  d_seq0_next[f] = d_seq0[f] + a_f (mod 2^32): the next
+   round's accept_flows reads its bases where this call left them.  d_img and d_img_next may
+   both be NULL (only the lengths and bases move); d_seq0 and d_seq0_next may both be NULL
+   (the bases are not moved).  The inputs are only read, nothing outside the three output
+   arrays is written and no byte outside the input image is loaded.  nflows == 1 reproduces
+   wtp_rx_advance.  nflows*window == 0 is valid, launches nothing and writes nothing.
+   WTP_EINVAL (before any device is touched, each with its own message): a limit exceeded as
+   above; exactly one of d_img and d_img_next, or of d_seq0 and d_seq0_next, NULL; a NULL
+   d_flow_adv, d_slot_len or d_slot_len_next with nflows*window > 0; an output range that
+   overlaps its input range: the slot_len arrays over 4*nflows*window bytes, the images over
+   1456*nflows*window, seq0 over 4*nflows.  Ranges that touch are valid.
+   One stream-ordered launch with no host synchronisation, allocation, scratch or library
+   table, and the independence of wtp_rx_advance; wtp_last_kernel() names
+   "k_rx_advance_flows".  Fast path: both images 16-B aligned; the v % 16 tail and every
+   other alignment move bytewise.  The cost follows the bytes that are filled. */
+int wtp_rx_advance_flows(const void *d_img, const uint32_t *d_slot_len,
+                         uint32_t nflows, uint32_t window, const uint64_t *d_flow_adv,
+                         const uint32_t *d_seq0,
+                         void *d_img_next, uint32_t *d_slot_len_next, uint32_t *d_seq0_next,
+                         void *stream);
 
 /* wtp_tx_advance slides the sender window's state (d_acked, d_sent_ms of
    wtp_tx_ingest_acks / wtp_tx_build_retransmit) down by a entries into d_acked_next /
