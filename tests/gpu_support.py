@@ -1,7 +1,8 @@
 """What the protocol GPU tests (tests/test_gpu_<call>.py) share: the library fixtures, the
 u32 conversions, guarded device buffers, the first-mismatch reporter, the graph capture and
 replay choreography, the record batch of the mixed-length calls, the guarded receive window
-and the device endpoints behind the model loops.  Nothing here is about one call; a new call's test file takes these
+and the device endpoints behind the model loops, and the sparse rings and periodic buffers of
+the tests past 4 GiB.  Nothing here is about one call; a new call's test file takes these
 from here and defines none of its own."""
 import numpy as np
 import pytest
@@ -486,3 +487,132 @@ class DevStreamEnd:
         self.offs += self.offs_out[:k].cpu().numpy().view(np.uint64).tolist()
         self.lens += u32(self.lens_out[:k]).tolist()
         return counts
+
+
+# ---- extents past 4 GiB -----------------------------------------------------------------------
+# What tests/test_gpu_wide.py shares: buffers whose extent passes 2^32 bytes while the work in
+# them stays small.  Every helper takes the two boundaries as an argument, so the CPU tests
+# (tests/test_gpu_support.py) run the same expectation code around a boundary of 2^12.
+BOUNDS = (1 << 31, 1 << 32)
+# 2049 * WIDE_STRIDE = 2^31 - 512 and 4098 * WIDE_STRIDE = 2^32 - 1024: a 1472-byte entry in
+# slot 2049 contains byte 2^31 and one in slot 4098 contains byte 2^32; stride % 16 == 0
+WIDE_STRIDE = (1 << 20) - 512
+# 2046 * ODD_STRIDE = 2^31 - 2 and 4092 * ODD_STRIDE = 2^32 - 4: an odd stride at which 16-byte
+# entries (ACKs) in slots 2046 and 4092 contain the boundaries
+ODD_STRIDE = 1049601
+WIDE_N = 4104       # slots of a WIDE_STRIDE ring: 4104 * WIDE_STRIDE > 2^32 + 6 MB
+PIECE = 512 << 20   # the most one device comparison looks at
+
+
+def slots(t, n, stride, width):
+    """The view (n, width) of the first `width` bytes of n slots `stride` bytes apart, from the
+    first byte of the byte tensor `t` on."""
+    assert n == 0 or (n - 1) * stride + width <= t.numel()
+    return t.as_strided((n, width), (stride, 1))
+
+
+class SparseRing:
+    """n slots of `stride` bytes that hold `fill`, at byte `off` of a 16-B aligned allocation
+    with `back` bytes of `fill` behind the last slot; rows (n x width bytes, on the ring's
+    device) go to the start of the slots.  `t` is the view from the ring's first byte on."""
+
+    def __init__(self, n, stride, rows=None, fill=0xEE, off=0, back=64, device="cuda"):
+        self.n, self.stride, self.fill, self.off = n, stride, fill, off
+        self.buf = torch.full((off + n * stride + back,), fill, dtype=torch.uint8, device=device)
+        assert self.buf.data_ptr() % 16 == 0
+        self.t = self.buf[off:]
+        if rows is not None:
+            slots(self.t, n, stride, rows.shape[1]).copy_(rows)
+
+    def rows(self, width, first=0, count=None):
+        count = self.n - first if count is None else count
+        return slots(self.t[first * self.stride:], count, self.stride, width)
+
+    def assert_rows(self, want, width=None):
+        """Slot i starts with want[i] (n x width, on the device; or a function of (a, b) that
+        makes rows a .. b - 1, with `width` given); every other byte of the allocation holds
+        `fill`: the slot tails, the bytes in front of the ring and behind it."""
+        n = self.n
+        if not callable(want):
+            assert want.shape[0] == n
+            rows, width = want, want.shape[1]
+            want = lambda a, b: rows[a:b]  # noqa: E731
+        per = max(1, PIECE // max(width, 1))
+        for a in range(0, n, per):
+            got, exp = self.rows(width, a, min(per, n - a)), want(a, min(a + per, n))
+            if not torch.equal(got, exp):
+                bad = torch.nonzero((got != exp).any(dim=1))[:5, 0].cpu().numpy() + a
+                raise AssertionError(f"slots {bad.tolist()} differ (byte offsets {[int(b) * self.stride for b in bad]})")
+        tail = self.stride - width
+        per = max(1, PIECE // max(tail, 1))
+        for a in range(0, n if tail else 0, per):
+            got = slots(self.t[a * self.stride + width:], min(per, n - a), self.stride, tail)
+            if not bool((got == self.fill).all()):
+                bad = torch.nonzero((got != self.fill).any(dim=1))[:5, 0].cpu().numpy() + a
+                raise AssertionError(f"the tails of slots {bad.tolist()} were written")
+        assert_filled(self.buf[:self.off], self.fill)
+        assert_filled(self.t[n * self.stride:], self.fill)
+
+
+def assert_filled(t, value, piece=PIECE):
+    """Every element of the 1-d tensor `t` equals `value`, looked at in pieces."""
+    for a in range(0, t.numel(), piece):
+        if not bool((t[a:a + piece] == value).all()):
+            first = a + int(torch.nonzero(t[a:a + piece] != value)[0, 0])
+            raise AssertionError(f"element {first} is {int(t[first])}, not {value}")
+
+
+def assert_straddles(starts, lens, stride, bounds=BOUNDS, contains=True):
+    """The batch whose entry i occupies bytes [starts[i], starts[i] + lens[i]) of its buffer has,
+    for each boundary B: a non-empty entry that ends in (B - stride, B], an entry that begins at
+    or above B and, with `contains` (where stride or offset can be chosen), an entry with
+    start < B < end."""
+    starts, lens = np.asarray(starts, dtype=np.int64), np.asarray(lens, dtype=np.int64)
+    ends = starts + lens
+    for b in bounds:
+        assert ((lens > 0) & (ends <= b) & (ends > b - stride)).any(), f"no entry ends just below {b:#x}"
+        assert (starts >= b).any(), f"no entry begins at or above {b:#x}"
+        assert not contains or ((starts < b) & (ends > b)).any(), f"no entry contains {b:#x}"
+
+
+def straddling_stride(start, width, step=1, bounds=BOUNDS):
+    """The first stride >= start (in steps of `step`) at which, for each boundary B, the entry
+    of `width` bytes in slot B // stride contains B: 0 < B % stride < width."""
+    stride = start
+    while not all(0 < b % stride < width for b in bounds):
+        stride += step
+    return stride
+
+
+def periodic(period, nbytes, off=0, device="cuda"):
+    """A Bytes of `nbytes` payload bytes at byte `off` of its allocation: the host array
+    `period` repeated on the device, cut at nbytes."""
+    mem = Bytes(fill=0, size=nbytes, off=off, device=device)
+    p = torch.from_numpy(np.ascontiguousarray(period, dtype=np.uint8)).to(device)
+    k, tail = divmod(nbytes, p.numel())
+    if k:
+        mem.payload[:k * p.numel()].view(k, p.numel()).copy_(p)
+    mem.payload[k * p.numel():].copy_(p[:tail])
+    return mem
+
+
+def periodic_crc(period, nbytes):
+    """crc32 of `period` repeated and cut at nbytes, from the oracle's CRC of one period (and
+    of the cut one at the end) folded on the host with concat_model.combine, by doubling."""
+    import concat_model
+    period = np.ascontiguousarray(period, dtype=np.uint8)
+    k, tail = divmod(nbytes, period.size)
+    acc, blk, blk_len = 0, O.crc32(period), period.size
+    while k:
+        if k & 1:
+            acc = concat_model.combine(acc, blk, blk_len)
+        blk, blk_len, k = concat_model.combine(blk, blk, blk_len), 2 * blk_len, k >> 1
+    return concat_model.combine(acc, O.crc32(period[:tail]), tail)
+
+
+def be_words(cols):
+    """(n, 4 * len(cols)) bytes: the int64 device tensors `cols` (values below 2^32) as
+    big-endian 32-bit words side by side, the layout of a header."""
+    w = torch.stack([c.to(torch.int64) for c in cols], dim=1)
+    sh = torch.tensor([24, 16, 8, 0], dtype=torch.int64, device=w.device)
+    return ((w[:, :, None] >> sh) & 0xFF).to(torch.uint8).reshape(w.shape[0], -1)

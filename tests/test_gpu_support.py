@@ -121,3 +121,76 @@ def test_mismatch_reporter():
     got[3 * 1472] ^= 1  # a later one changes the count only
     with pytest.raises(AssertionError, match=r"^2 bytes differ, first at 2961: unit 2, byte 17 \(context\)$"):
         assert_bytes_equal(got, want, 1472, "context")
+
+
+# ---- the helpers of tests/test_gpu_wide.py, with 2^12 and 2^13 in place of 2^31 and 2^32 --------
+SMALL_BOUNDS = (1 << 12, 1 << 13)
+
+
+@pytest.mark.parametrize("nbytes", [0, 1, 99, 100, 101, (1 << 12) + 37, (1 << 13) + 5, 10 * 100])
+@pytest.mark.parametrize("off", [0, 5])
+def test_periodic_buffer_and_its_crc(nbytes, off):
+    from gpu_support import periodic, periodic_crc
+    period = O.synth_fill_np(100, start_byte=7)
+    mem = periodic(period, nbytes, off=off, device="cpu")
+    want = np.tile(period, nbytes // 100 + 1)[:nbytes]
+    assert mem.t.data_ptr() % 16 == off and np.array_equal(mem.get(), want)
+    assert periodic_crc(period, nbytes) == O.crc32(want)
+
+
+def test_sparse_ring_and_its_check():
+    from gpu_support import SparseRing, be_words, slots
+    n, stride, width = 37, 240, 24   # 37 * 240 > 2^13
+    rng = np.random.default_rng(5)
+    host_rows = rng.integers(0, 256, (n, width), dtype=np.uint8)
+    host_rows[host_rows == 0xEE] = 1
+    rows = torch.from_numpy(host_rows)
+    want = np.full(3 + n * stride + 64, 0xEE, np.uint8)
+    for i in range(n):
+        want[3 + i * stride:3 + i * stride + width] = host_rows[i]
+
+    def fresh():
+        r = SparseRing(n, stride, rows, off=3, device="cpu")
+        assert r.t.data_ptr() % 16 == 3 and np.array_equal(r.buf.numpy(), want)
+        return r
+
+    fresh().assert_rows(rows)
+    fresh().assert_rows(lambda a, b: rows[a:b], width)
+    assert torch.equal(fresh().rows(width, 17, 2), rows[17:19])
+    assert torch.equal(slots(fresh().t, n, stride, width), rows)
+    # one changed byte anywhere is noticed: in a row, in a tail just below a boundary, in front, behind
+    for at in (3 + 17 * stride + 5, 3 + 17 * stride + width, (1 << 12) - 1, (1 << 13) - 1, 0, 2, 3 + n * stride,
+               3 + n * stride + 63):
+        r = fresh()
+        r.buf[at] ^= 0x10
+        with pytest.raises(AssertionError):
+            r.assert_rows(rows)
+    got = be_words([torch.tensor([2, 0x01020304]), torch.tensor([0xFFFFFFFF, 7])]).numpy()
+    assert got.tolist() == [[0, 0, 0, 2, 255, 255, 255, 255], [1, 2, 3, 4, 0, 0, 0, 7]]
+
+
+def test_assert_filled_and_straddles():
+    from gpu_support import assert_filled, assert_straddles
+    t = torch.full((1000,), 9, dtype=torch.uint8)
+    assert_filled(t, 9, piece=64)
+    t[777] = 8
+    with pytest.raises(AssertionError, match="element 777 is 8"):
+        assert_filled(t, 9, piece=64)
+    stride = 240
+    starts = np.arange(37) * stride
+    lens = np.full(37, 200)
+    # 17 * 240 = 4080 < 4096 < 4280 and 34 * 240 = 8160 < 8192 < 8360
+    assert_straddles(starts, lens, stride, SMALL_BOUNDS)
+    for drop in (16, 17, 34):   # the entry that ends below 2^12, and the ones that contain 2^12 and 2^13
+        keep = np.arange(37) != drop
+        short = np.where(keep, lens, 0)
+        with pytest.raises(AssertionError):
+            assert_straddles(starts, short, stride, SMALL_BOUNDS)
+    with pytest.raises(AssertionError, match="begins at or above 0x2000"):
+        assert_straddles(starts[:35], lens[:35], stride, SMALL_BOUNDS)
+    from gpu_support import BOUNDS, ODD_STRIDE, WIDE_N, WIDE_STRIDE, straddling_stride
+    assert_straddles(np.arange(4100) * ODD_STRIDE, np.full(4100, 16), ODD_STRIDE, BOUNDS)
+    assert straddling_stride(240, 200, bounds=SMALL_BOUNDS) == 240 and straddling_stride(256, 200, bounds=SMALL_BOUNDS) == 260
+    assert straddling_stride(WIDE_STRIDE, 1025, step=16) == WIDE_STRIDE and WIDE_STRIDE % 16 == 0
+    assert_straddles(np.arange(WIDE_N) * WIDE_STRIDE, np.full(WIDE_N, 1472), WIDE_STRIDE, BOUNDS)
+    assert_straddles(np.arange(40) * 256, np.full(40, 256), 256, SMALL_BOUNDS, contains=False)  # a stride that divides them
