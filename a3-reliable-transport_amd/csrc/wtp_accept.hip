@@ -172,16 +172,13 @@ extern "C" int wtp_accept_data_packets(const void *d_dgrams, size_t stride, cons
     if (rc) return rc;
     {
         const uint64_t blocks = std::max<uint64_t>(1, (uint64_t(n) + 255) / 256);
-        hipLaunchKernelGGL(dev::k_accept_claim, dim3(unsigned(blocks)), dim3(256), 0, st, ring, uint64_t(stride),
-                           d_recv_len, d_ok, uint64_t(n), seq0, window, d_slot_len, d_ack);
-        if ((rc = launch_check("k_accept_claim"))) return rc;
+        rc = launch("k_accept_claim", dev::k_accept_claim, dim3(unsigned(blocks)), dim3(256), st, ring, uint64_t(stride),
+                    d_recv_len, d_ok, uint64_t(n), seq0, window, d_slot_len, d_ack);
+        if (rc) return rc;
     }
     // one 16-lane group per datagram; at least enough lanes to scan a small window at once
     const uint64_t scan = d_ack ? std::min<uint64_t>((uint64_t(window) + 255) / 256, 1024) : 0;
     const uint64_t blocks = std::max<uint64_t>({1, (uint64_t(n) * dev::kGroup + 255) / 256, scan});
-    hipLaunchKernelGGL(dev::k_accept_place, dim3(unsigned(blocks)), dim3(256), 0, st, ring, uint64_t(stride),
-                       d_recv_len, d_ok, uint64_t(n), seq0, window, static_cast<uint8_t *>(d_out), d_slot_len, d_place,
-                       d_ack);
-    wtp_set_kernel_("k_accept_place");
-    return launch_check("k_accept_place");
+    return launch("k_accept_place", dev::k_accept_place, dim3(unsigned(blocks)), dim3(256), st, ring, uint64_t(stride),
+                  d_recv_len, d_ok, uint64_t(n), seq0, window, static_cast<uint8_t *>(d_out), d_slot_len, d_place, d_ack);
 }

@@ -196,29 +196,30 @@ k_ack_emit(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t *__
 
 namespace {
 
-// d_work of wtp_rx_build_acks, from align4 on: blk[nblk], then in
-// cumulative mode T[window] and bmax[wblk].
+// d_work of wtp_rx_build_acks: blk[nblk], then in cumulative mode T[window] and bmax[wblk].
 struct AckWork {
     uint32_t nblk, wblk;
-    size_t blk, T, bmax, bytes;
+    uint32_t *blk, *T, *bmax;
+    size_t bytes;
 };
 
-AckWork ack_layout(size_t n, uint32_t window, uint32_t mode) {
+AckWork ack_layout(void *d_work, size_t n, uint32_t window, uint32_t mode) {
     AckWork w;
+    wtp::Work l(d_work, 4);
     const uint32_t slots = mode == WTP_ACK_SELECTIVE ? 0u : window;
     w.nblk = uint32_t((n + wtp::dev::kAckBlock - 1) / wtp::dev::kAckBlock);
     w.wblk = (slots + wtp::dev::kAckBlock - 1) / wtp::dev::kAckBlock;
-    w.blk = 0;
-    w.T = size_t(w.nblk) * 4;
-    w.bmax = w.T + size_t(slots) * 4;
-    w.bytes = wtp::kWorkSlack + w.bmax + size_t(w.wblk) * 4;
+    w.blk = l.take<uint32_t>(w.nblk);
+    w.T = l.take<uint32_t>(slots);
+    w.bmax = l.take<uint32_t>(w.wblk);
+    w.bytes = l.bytes();
     return w;
 }
 
 }  // namespace
 
 extern "C" size_t wtp_rx_ack_work_bytes(size_t n, uint32_t window, uint32_t mode) {
-    return ack_layout(std::min<size_t>(n, WTP_RX_MAX_BATCH), std::min<uint32_t>(window, WTP_RX_MAX_WINDOW), mode).bytes;
+    return ack_layout(nullptr, std::min<size_t>(n, WTP_RX_MAX_BATCH), std::min<uint32_t>(window, WTP_RX_MAX_WINDOW), mode).bytes;
 }
 
 extern "C" int wtp_rx_build_acks(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len, size_t n,
@@ -234,8 +235,8 @@ extern "C" int wtp_rx_build_acks(const void *d_dgrams, size_t stride, const uint
     if (cum && window > WTP_RX_MAX_WINDOW) return fail(WTP_EINVAL, "window %u > %u", window, WTP_RX_MAX_WINDOW);
     if ((rc = check_stride(stride))) return rc;
     if (ack_stride < 16) return fail(WTP_EINVAL, "ack_stride %zu < 16", ack_stride);
-    const AckWork w = ack_layout(n, window, mode);
-    if (work_bytes < w.bytes) return fail(WTP_EINVAL, "work_bytes %zu < %zu", work_bytes, w.bytes);
+    const AckWork w = ack_layout(d_work, n, window, mode);
+    if ((rc = check_work_bytes(work_bytes, w.bytes))) return rc;
     if (!d_counts || !d_work) return fail(WTP_EINVAL, "null pointer");
     if (n > 0) {
         if ((rc = check_ring(d_dgrams, stride, d_recv_len, d_ok))) return rc;
@@ -244,33 +245,25 @@ extern "C" int wtp_rx_build_acks(const void *d_dgrams, size_t stride, const uint
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint8_t *ring = static_cast<const uint8_t *>(d_dgrams);
-    uint8_t *work = align4(d_work);
-    uint32_t *blk = reinterpret_cast<uint32_t *>(work + w.blk);
-    uint32_t *bmax = reinterpret_cast<uint32_t *>(work + w.bmax);
     // T: cumulative mode with datagrams and a window; otherwise no slot is ever looked up
-    uint32_t *T = cum && n > 0 && window > 0 ? reinterpret_cast<uint32_t *>(work + w.T) : nullptr;
+    uint32_t *T = cum && n > 0 && window > 0 ? w.T : nullptr;
     const uint32_t n32 = uint32_t(n);
     if (T) {
-        hipLaunchKernelGGL(dev::k_ack_init, dim3((window + 255) / 256), dim3(256), 0, st, d_slot_len, window, T);
-        if ((rc = launch_check("k_ack_init"))) return rc;
+        if ((rc = launch("k_ack_init", dev::k_ack_init, dim3((window + 255) / 256), dim3(256), st, d_slot_len, window, T))) return rc;
     }
     if (n > 0) {
-        hipLaunchKernelGGL(dev::k_ack_mark, dim3(w.nblk), dim3(dev::kAckBlock), 0, st, ring, uint64_t(stride), d_recv_len,
-                           d_ok, n32, seq0, window, d_place, T, blk);
-        if ((rc = launch_check("k_ack_mark"))) return rc;
+        rc = launch("k_ack_mark", dev::k_ack_mark, dim3(w.nblk), dim3(dev::kAckBlock), st, ring, uint64_t(stride), d_recv_len,
+                    d_ok, n32, seq0, window, d_place, T, w.blk);
+        if (rc) return rc;
     }
     if (T) {
-        hipLaunchKernelGGL(dev::k_ack_bmax, dim3(w.wblk), dim3(dev::kAckBlock), 0, st, T, window, bmax);
-        if ((rc = launch_check("k_ack_bmax"))) return rc;
-        hipLaunchKernelGGL(dev::k_ack_scan, dim3(w.wblk), dim3(dev::kAckBlock), 0, st, T, window, bmax);
-        if ((rc = launch_check("k_ack_scan"))) return rc;
+        if ((rc = launch("k_ack_bmax", dev::k_ack_bmax, dim3(w.wblk), dim3(dev::kAckBlock), st, T, window, w.bmax))) return rc;
+        if ((rc = launch("k_ack_scan", dev::k_ack_scan, dim3(w.wblk), dim3(dev::kAckBlock), st, T, window, w.bmax))) return rc;
     }
     // n == 0: one block, which only writes d_counts = {0, 0}.  The kernel picks the 16-B
     // store per slot from the slot's own address: with an aligned ring and ack_stride % 16
     // == 0 that is every slot, otherwise only a slot that happens to be aligned.
-    hipLaunchKernelGGL(dev::k_ack_emit, dim3(std::max(w.nblk, 1u)), dim3(dev::kAckBlock), 0, st, ring, uint64_t(stride),
-                       d_recv_len, d_ok, n32, mode, seq0, window, T, blk, w.nblk,
-                       static_cast<uint8_t *>(d_ack_wire), uint64_t(ack_stride), skip, max_acks, d_src, d_counts);
-    wtp_set_kernel_("k_ack_emit");
-    return launch_check("k_ack_emit");
+    return launch("k_ack_emit", dev::k_ack_emit, dim3(std::max(w.nblk, 1u)), dim3(dev::kAckBlock), st, ring, uint64_t(stride),
+                  d_recv_len, d_ok, n32, mode, seq0, window, T, w.blk, w.nblk, static_cast<uint8_t *>(d_ack_wire),
+                  uint64_t(ack_stride), skip, max_acks, d_src, d_counts);
 }

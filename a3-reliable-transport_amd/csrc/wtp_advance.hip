@@ -130,16 +130,6 @@ k_tx_advance(const uint32_t *__restrict__ acked, const uint32_t *__restrict__ se
 }  // namespace dev
 }  // namespace wtp
 
-namespace {
-
-// [p, p + bytes) and [q, q + bytes) share a byte (bytes > 0)
-bool overlap(const void *p, const void *q, uint64_t bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(p), y = reinterpret_cast<uintptr_t>(q);
-    return x < y ? y - x < bytes : x - y < bytes;
-}
-
-}  // namespace
-
 extern "C" int wtp_rx_advance(const void *d_img, const uint32_t *d_slot_len, uint32_t window, const uint64_t *d_adv,
                               void *d_img_next, uint32_t *d_slot_len_next, void *stream) {
     using namespace wtp;
@@ -158,11 +148,9 @@ extern "C" int wtp_rx_advance(const void *d_img, const uint32_t *d_slot_len, uin
     const uint32_t groups = ((window + 63) / 64 + dev::kAdvWaves - 1) / dev::kAdvWaves;
     const unsigned blocks = std::min(groups, dev::kAdvMaxBlocks);
     const uint32_t vec = ((reinterpret_cast<uintptr_t>(d_img) | reinterpret_cast<uintptr_t>(d_img_next)) & 15u) == 0;
-    hipLaunchKernelGGL(dev::k_rx_advance, dim3(blocks), dim3(dev::kAdvBlock), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const uint8_t *>(d_img), d_slot_len, window, d_adv, static_cast<uint8_t *>(d_img_next),
-                       d_slot_len_next, vec);
-    wtp_set_kernel_("k_rx_advance");
-    return launch_check("k_rx_advance");
+    return launch("k_rx_advance", dev::k_rx_advance, dim3(blocks), dim3(dev::kAdvBlock), static_cast<hipStream_t>(stream),
+                  static_cast<const uint8_t *>(d_img), d_slot_len, window, d_adv, static_cast<uint8_t *>(d_img_next),
+                  d_slot_len_next, vec);
 }
 
 extern "C" int wtp_tx_advance(const uint32_t *d_acked, const uint32_t *d_sent_ms, uint32_t slots, const uint32_t *d_adv,
@@ -184,8 +172,6 @@ extern "C" int wtp_tx_advance(const uint32_t *d_acked, const uint32_t *d_sent_ms
                 return fail(WTP_EINVAL, "%s overlaps %s (slots %u)", out_name[o], in_name[i], slots);
     if (overlap(d_acked_next, d_sent_ms_next, uint64_t(slots) * 4))
         return fail(WTP_EINVAL, "d_sent_ms_next overlaps d_acked_next (slots %u)", slots);
-    hipLaunchKernelGGL(dev::k_tx_advance, dim3((slots + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), d_acked,
-                       d_sent_ms, slots, d_adv, fill_ms, d_acked_next, d_sent_ms_next);
-    wtp_set_kernel_("k_tx_advance");
-    return launch_check("k_tx_advance");
+    return launch("k_tx_advance", dev::k_tx_advance, dim3((slots + 255) / 256), dim3(256), static_cast<hipStream_t>(stream),
+                  d_acked, d_sent_ms, slots, d_adv, fill_ms, d_acked_next, d_sent_ms_next);
 }

@@ -1,6 +1,6 @@
-// wtp_common.hpp — what the protocol translation units (wtp_accept.hip, wtp_concat.hip,
-// wtp_tx.hip, wtp_txvar.hip, wtp_ack.hip, wtp_buildvar.hip, wtp_deliver.hip, wtp_advance.hip, wtp_flows.hip, wtp_flows_flush.hip) share: error plumbing and argument checks on the host, and on
-// the device the header's wire format and the wave reductions.
+// wtp_common.hpp — what the protocol translation units (PROTO in the Makefile) share: on the
+// host the error plumbing, the launch helper, the argument checks and the d_work layout, and
+// on the device the header's wire format, the wave reductions and a few one-line helpers.
 // Internal: the C-ABI is include/wtp_crc32.h.
 //
 // Each protocol call is a separate translation unit: k_fixed_braid and everything it
@@ -12,6 +12,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "wtp_crc32.h"
 
@@ -37,12 +38,34 @@ inline int launch_check(const char *what) {
     return WTP_OK;
 }
 
-// A caller's d_work may be 1-B aligned: its words start at the first 4-B boundary, and a
-// layout asks for kWorkSlack bytes more than it holds.
-constexpr size_t kWorkSlack = 4;
-inline uint8_t *align4(void *d_work) {
-    return reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_work) + 3) & ~uintptr_t(3));
+// Every launch of the protocol units: launches, records `name` for wtp_last_kernel() and
+// returns launch_check(name), so after a launch that itself fails the name is that launch's.
+// The arguments convert to the kernel's parameter types as they do at a direct call.  Always
+// inlined: left to itself the compiler emits one out-of-line copy per kernel signature.
+template <class... P>
+__attribute__((always_inline)) inline int launch(const char *name, void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t st,
+                  std::type_identity_t<P>... args) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
+    wtp_set_kernel_(name);
+    return launch_check(name);
 }
+
+// The layout of a call's d_work: consecutive arrays from the first `align`-byte boundary (4,
+// or 16 where a kernel reads 16-B vectors).  A caller's d_work may be 1-B aligned, so a layout
+// asks for `align` bytes more than it holds.  With a NULL d_work only bytes() means anything.
+// The order of the arrays is the layout's: each must start at a multiple of its element size.
+struct Work {
+    uintptr_t base;
+    size_t align, end = 0;
+    Work(void *d_work, size_t a) : base((reinterpret_cast<uintptr_t>(d_work) + a - 1) & ~uintptr_t(a - 1)), align(a) {}
+    template <class T>
+    T *take(size_t count) {
+        T *p = reinterpret_cast<T *>(base + end);
+        end += count * sizeof(T);
+        return p;
+    }
+    size_t bytes() const { return align + end; }
+};
 
 // The checks of a datagram ring's arguments.  Each is its own call because the entry points
 // interleave them with their own checks, and which message two bad arguments give is part
@@ -64,9 +87,28 @@ inline int check_ring(const void *d_dgrams, size_t stride, const uint32_t *d_rec
     return check_stride(stride);
 }
 
+inline int check_work_bytes(size_t work_bytes, size_t need) {
+    return work_bytes < need ? fail(WTP_EINVAL, "work_bytes %zu < %zu", work_bytes, need) : WTP_OK;
+}
+inline int null_arg(const char *name) { return fail(WTP_EINVAL, "null pointer: %s", name); }
+// the multi-connection state: flow f owns global slots [f * window, (f + 1) * window)
+inline int check_flows(uint32_t nflows, uint32_t window) {
+    if (nflows > WTP_RX_MAX_FLOWS) return fail(WTP_EINVAL, "nflows %u > %u", nflows, WTP_RX_MAX_FLOWS);
+    if (window > WTP_RX_MAX_WINDOW) return fail(WTP_EINVAL, "window %u > %u", window, WTP_RX_MAX_WINDOW);
+    if (uint64_t(nflows) * window > WTP_RX_MAX_FLOW_SLOTS)
+        return fail(WTP_EINVAL, "nflows %u * window %u > %u slots", nflows, window, WTP_RX_MAX_FLOW_SLOTS);
+    return WTP_OK;
+}
+// [p, p + bytes) and [q, q + bytes) share a byte (bytes > 0)
+inline bool overlap(const void *p, const void *q, uint64_t bytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(p), y = reinterpret_cast<uintptr_t>(q);
+    return x < y ? y - x < bytes : x - y < bytes;
+}
+
 namespace dev {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // a 16-B load of dword alignment
 
 __device__ __forceinline__ uint32_t be32(const uint8_t *p) {
     return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | uint32_t(p[3]);
@@ -88,6 +130,20 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v = min(v, uint32_t(__shfl_xor(v, d, 64)));
     return v;
+}
+
+// Orders a wave's LDS stores before its later LDS loads of other lanes' data (and the
+// reverse); a wave's DS instructions execute in order, so this binds only the compiler.
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Bytes [0, n) of a 16-byte vector as masks of its low and high half.
+__device__ __forceinline__ uint64_t below_lo(uint32_t n) { return n >= 8 ? ~uint64_t(0) : (uint64_t(1) << (8 * n)) - 1; }
+__device__ __forceinline__ uint64_t below_hi(uint32_t n) {
+    return n <= 8 ? 0 : n >= 16 ? ~uint64_t(0) : (uint64_t(1) << (8 * (n - 8))) - 1;
 }
 
 // ---- the 16-byte header: htonl{type, seqNum, length, checksum} ---------------------------

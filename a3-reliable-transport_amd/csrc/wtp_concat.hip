@@ -323,20 +323,15 @@ int launch_fold(const uint32_t *src, uint64_t n, uint32_t len_r, const dev::Edge
     const dev::FoldArgs f = plan_fold(src, n, len_r);
     const dev::EdgeArgs none{};
     const dev::EdgeArgs &e0 = nedge > 0 ? edges[0] : none, &e1 = nedge > 1 ? edges[1] : none;
-    wtp_set_kernel_("k_concat_fold");
-    if (f.groups == 1 && nedge == 0) {
-        hipLaunchKernelGGL(dev::k_concat_fold, dim3(1), dim3(dev::kCcThreads), 0, st, f, none, none, work, fin);
-        return launch_check("k_concat_fold");
-    }
-    hipLaunchKernelGGL(dev::k_concat_fold, dim3(f.groups + nedge), dim3(dev::kCcThreads), 0, st, f, e0, e1, work,
-                       dev::FinalArgs{});
-    int rc = launch_check("k_concat_fold");
+    if (f.groups == 1 && nedge == 0)
+        return launch("k_concat_fold", dev::k_concat_fold, dim3(1), dim3(dev::kCcThreads), st, f, none, none, work, fin);
+    int rc = launch("k_concat_fold", dev::k_concat_fold, dim3(f.groups + nedge), dim3(dev::kCcThreads), st, f, e0, e1, work,
+                    dev::FinalArgs{});
     if (rc) return rc;
     // the partials: f.groups elements of 256 * run payloads each
     const uint32_t len2 = gf::reduce(uint64_t(len_r) * gf::reduce(dev::kCcThreads * f.run));
     const dev::FoldArgs f2 = plan_fold(work, f.groups, len2);  // <= 1024 elements: one workgroup
-    hipLaunchKernelGGL(dev::k_concat_fold, dim3(1), dim3(dev::kCcThreads), 0, st, f2, none, none, work, fin);
-    return launch_check("k_concat_fold");
+    return launch("k_concat_fold", dev::k_concat_fold, dim3(1), dim3(dev::kCcThreads), st, f2, none, none, work, fin);
 }
 
 int check_work(const void *d_work, size_t work_bytes, size_t need) {
@@ -380,19 +375,15 @@ extern "C" int wtp_crc32_concat(const uint32_t *d_crc, const uint32_t *d_len, ui
         run = std::max<uint64_t>(dev::kCcRun, ceil_div(n, uint64_t(dev::kCcThreads) * dev::kCcMaxGroups));
         groups = uint32_t(ceil_div(n, dev::kCcThreads * run));
     }
-    wtp_set_kernel_("k_concat_var");
-    if (groups == 1) {
-        hipLaunchKernelGGL(dev::k_concat_var, dim3(1), dim3(dev::kCcThreads), 0, st, d_crc, d_len, uint64_t(n), run, pw,
-                           work, work + dev::kCcWorkLen, d_out);
-        return launch_check("k_concat_var");
-    }
-    hipLaunchKernelGGL(dev::k_concat_var, dim3(groups), dim3(dev::kCcThreads), 0, st, d_crc, d_len, uint64_t(n), run, pw,
-                       work, work + dev::kCcWorkLen, static_cast<uint32_t *>(nullptr));
-    if ((rc = launch_check("k_concat_var"))) return rc;
-    hipLaunchKernelGGL(dev::k_concat_var, dim3(1), dim3(dev::kCcThreads), 0, st, static_cast<const uint32_t *>(work),
-                       static_cast<const uint32_t *>(work + dev::kCcWorkLen), uint64_t(groups),
-                       ceil_div(groups, dev::kCcThreads), pw, work, work + dev::kCcWorkLen, d_out);
-    return launch_check("k_concat_var");
+    if (groups == 1)
+        return launch("k_concat_var", dev::k_concat_var, dim3(1), dim3(dev::kCcThreads), st, d_crc, d_len, uint64_t(n), run, pw,
+                      work, work + dev::kCcWorkLen, d_out);
+    rc = launch("k_concat_var", dev::k_concat_var, dim3(groups), dim3(dev::kCcThreads), st, d_crc, d_len, uint64_t(n), run, pw,
+                work, work + dev::kCcWorkLen, static_cast<uint32_t *>(nullptr));
+    if (rc) return rc;
+    return launch("k_concat_var", dev::k_concat_var, dim3(1), dim3(dev::kCcThreads), st, static_cast<const uint32_t *>(work),
+                  static_cast<const uint32_t *>(work + dev::kCcWorkLen), uint64_t(groups), ceil_div(groups, dev::kCcThreads),
+                  pw, work, work + dev::kCcWorkLen, d_out);
 }
 
 extern "C" int wtp_crc32_buffer(const void *d_buf, size_t nbytes, void *d_work, size_t work_bytes, uint32_t *d_out,

@@ -70,8 +70,6 @@ constexpr uint32_t kDlRound = 64 * kDlVecs;  // vectors per wave and round (4 Ki
 constexpr uint32_t kDlMaxBlocks = 2048;  // the capped grid: eight workgroups per CU (62 VGPRs), 32 MiB of the stream per pass
 constexpr uint32_t kDlStage = 256;      // prefix sums a wave keeps in LDS per round
 
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // a 16-B load of dword alignment
-
 __global__ void __launch_bounds__(kDlBlock)
 k_deliver_bsum(const uint32_t *__restrict__ slot_len, uint32_t window, uint32_t *__restrict__ bsum,
                uint32_t *__restrict__ bend) {
@@ -167,14 +165,6 @@ k_deliver_scan(const uint32_t *__restrict__ slot_len, uint32_t window, uint32_t 
     }
 }
 
-// Orders a wave's LDS stores before its later LDS loads of other lanes' data (and the
-// reverse); a wave's DS instructions execute in order, so this binds only the compiler.
-__device__ __forceinline__ void dl_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // The last index in [lo, hi] whose P is <= b (P[lo] <= b is the caller's); p(i) = P[i].
 template <class Get>
 __device__ __forceinline__ uint32_t dl_owner(Get p, uint32_t lo, uint32_t hi, uint32_t b) {
@@ -203,12 +193,6 @@ __device__ __forceinline__ uint32_t dl_owner_wave(const uint32_t *__restrict__ P
         hi = min(hi, lo + step - 1);
     }
     return lo;
-}
-
-// Bytes [0, n) of a 16-byte vector as masks of its low and high half.
-__device__ __forceinline__ uint64_t dl_below_lo(uint32_t n) { return n >= 8 ? ~uint64_t(0) : (uint64_t(1) << (8 * n)) - 1; }
-__device__ __forceinline__ uint64_t dl_below_hi(uint32_t n) {
-    return n <= 8 ? 0 : n >= 16 ? ~uint64_t(0) : (uint64_t(1) << (8 * (n - 8))) - 1;
 }
 
 // Delivered bytes [b0, b1), b1 - b0 <= 16, as bytes [skip, skip + b1 - b0) of a vector, piece
@@ -248,8 +232,8 @@ __device__ __forceinline__ u32x4 dl_merge(const uint8_t *__restrict__ img, uint3
                     vhi |= byte << (8 * (pos + q - 8));
             }
         }
-        lo |= vlo & dl_below_lo(pos + nb) & ~dl_below_lo(pos);
-        hi |= vhi & dl_below_hi(pos + nb) & ~dl_below_hi(pos);
+        lo |= vlo & below_lo(pos + nb) & ~below_lo(pos);
+        hi |= vhi & below_hi(pos + nb) & ~below_hi(pos);
         j = end;
     }
     u32x4 r;
@@ -289,7 +273,7 @@ k_deliver_copy(const uint8_t *__restrict__ img, uint32_t img_bytes, uint32_t vec
         const bool staged = cnt <= kDlStage;
         if (staged)
             for (uint32_t i = lane; i < cnt; i += 64) s_P[wv][i] = P[olo + i];
-        dl_wave_sync();
+        wave_sync();
         // the round over p(i) = P[i]: from LDS, or from memory (two bodies: one pointer, one address space each)
         auto body = [&](auto p) {
         uint32_t b0[kDlVecs], b1[kDlVecs], own[kDlVecs], sh[kDlVecs], soff[kDlVecs];
@@ -366,7 +350,7 @@ k_deliver_copy(const uint8_t *__restrict__ img, uint32_t img_bytes, uint32_t vec
             body([&](uint32_t i) { return sp[i - olo]; });
         else
             body([&](uint32_t i) { return P[i]; });
-        dl_wave_sync();  // the next round's s_P stores follow these loads
+        wave_sync();  // the next round's s_P stores follow these loads
     }
 }
 
@@ -375,28 +359,29 @@ k_deliver_copy(const uint8_t *__restrict__ img, uint32_t img_bytes, uint32_t vec
 
 namespace {
 
-// d_work of wtp_rx_deliver, from align4 on: hdr[4] = {k, P[k], -, -}, bsum[nblk],
-// bend[nblk], P[window + 1].
+// d_work of wtp_rx_deliver: hdr[4] = {k, P[k], -, -}, bsum[nblk], bend[nblk], P[window + 1].
 struct DeliverWork {
     uint32_t nblk;
-    size_t hdr, bsum, bend, P, bytes;
+    uint32_t *hdr, *bsum, *bend, *P;
+    size_t bytes;
 };
 
-DeliverWork deliver_layout(uint32_t window) {
+DeliverWork deliver_layout(void *d_work, uint32_t window) {
     DeliverWork w;
+    wtp::Work l(d_work, 4);
     w.nblk = (window + wtp::dev::kDlBlock - 1) / wtp::dev::kDlBlock;
-    w.hdr = 0;
-    w.bsum = 16;
-    w.bend = w.bsum + size_t(w.nblk) * 4;
-    w.P = w.bend + size_t(w.nblk) * 4;
-    w.bytes = wtp::kWorkSlack + w.P + (size_t(window) + 1) * 4;
+    w.hdr = l.take<uint32_t>(4);
+    w.bsum = l.take<uint32_t>(w.nblk);
+    w.bend = l.take<uint32_t>(w.nblk);
+    w.P = l.take<uint32_t>(size_t(window) + 1);
+    w.bytes = l.bytes();
     return w;
 }
 
 }  // namespace
 
 extern "C" size_t wtp_rx_deliver_work_bytes(uint32_t window) {
-    return deliver_layout(std::min<uint32_t>(window, WTP_RX_MAX_WINDOW)).bytes;
+    return deliver_layout(nullptr, std::min<uint32_t>(window, WTP_RX_MAX_WINDOW)).bytes;
 }
 
 extern "C" int wtp_rx_deliver(const void *d_img, const uint32_t *d_slot_len, uint32_t window, uint32_t max_slots,
@@ -407,10 +392,11 @@ extern "C" int wtp_rx_deliver(const void *d_img, const uint32_t *d_slot_len, uin
     if (window > WTP_RX_MAX_WINDOW) return fail(WTP_EINVAL, "window %u > %u", window, WTP_RX_MAX_WINDOW);
     if (stream_off > stream_bytes)
         return fail(WTP_EINVAL, "stream_off %llu > stream_bytes %zu", static_cast<unsigned long long>(stream_off), stream_bytes);
-    const DeliverWork w = deliver_layout(window);
-    if (work_bytes < w.bytes) return fail(WTP_EINVAL, "work_bytes %zu < %zu", work_bytes, w.bytes);
-    if (!d_counts) return fail(WTP_EINVAL, "null pointer: d_counts");
-    if (!d_work) return fail(WTP_EINVAL, "null pointer: d_work");
+    const DeliverWork w = deliver_layout(d_work, window);
+    int rc = check_work_bytes(work_bytes, w.bytes);
+    if (rc) return rc;
+    if (!d_counts) return null_arg("d_counts");
+    if (!d_work) return null_arg("d_work");
     if (window > 0) {
         if (!d_img) return fail(WTP_EINVAL, "null pointer: d_img with window %u", window);
         if (!d_slot_len) return fail(WTP_EINVAL, "null pointer: d_slot_len with window %u", window);
@@ -418,22 +404,16 @@ extern "C" int wtp_rx_deliver(const void *d_img, const uint32_t *d_slot_len, uin
             return fail(WTP_EINVAL, "null pointer: d_stream with window %u and max_slots %u", window, max_slots);
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    uint8_t *work = align4(d_work);
-    uint32_t *hdr = reinterpret_cast<uint32_t *>(work + w.hdr);
-    uint32_t *bsum = reinterpret_cast<uint32_t *>(work + w.bsum);
-    uint32_t *bend = reinterpret_cast<uint32_t *>(work + w.bend);
-    uint32_t *P = reinterpret_cast<uint32_t *>(work + w.P);
-    int rc;
     if (window > 0) {
-        hipLaunchKernelGGL(dev::k_deliver_bsum, dim3(w.nblk), dim3(dev::kDlBlock), 0, st, d_slot_len, window, bsum, bend);
-        if ((rc = launch_check("k_deliver_bsum"))) return rc;
+        if ((rc = launch("k_deliver_bsum", dev::k_deliver_bsum, dim3(w.nblk), dim3(dev::kDlBlock), st, d_slot_len, window,
+                         w.bsum, w.bend)))
+            return rc;
     }
     // window == 0: one block, which only writes d_counts = {0, 0, 0, 0}
-    hipLaunchKernelGGL(dev::k_deliver_scan, dim3(window / dev::kDlBlock + 1), dim3(dev::kDlBlock), 0, st, d_slot_len, window,
-                       max_slots, stream_off, uint64_t(stream_bytes) - stream_off, bsum, bend, w.nblk, P, hdr, d_offsets_out,
-                       d_lengths_out, d_counts);
-    wtp_set_kernel_("k_deliver_scan");
-    if ((rc = launch_check("k_deliver_scan")) || window == 0 || max_slots == 0) return rc;
+    rc = launch("k_deliver_scan", dev::k_deliver_scan, dim3(window / dev::kDlBlock + 1), dim3(dev::kDlBlock), st, d_slot_len,
+                window, max_slots, stream_off, uint64_t(stream_bytes) - stream_off, w.bsum, w.bend, w.nblk, w.P, w.hdr,
+                d_offsets_out, d_lengths_out, d_counts);
+    if (rc || window == 0 || max_slots == 0) return rc;
     // the grid from what the arguments allow, never from d_counts: min(window, max_slots)
     // full slots, capped; a workgroup leaves at once when the scan delivered fewer bytes
     const uintptr_t first = reinterpret_cast<uintptr_t>(d_stream) + stream_off;
@@ -442,8 +422,7 @@ extern "C" int wtp_rx_deliver(const void *d_img, const uint32_t *d_slot_len, uin
     const uint64_t groups = (most + 16 * dev::kDlRound * (dev::kDlCopyBlock / 64) - 1) / (16 * dev::kDlRound * (dev::kDlCopyBlock / 64));
     const unsigned blocks = unsigned(std::min<uint64_t>(groups, dev::kDlMaxBlocks));
     const uint32_t vec = (reinterpret_cast<uintptr_t>(d_img) & 3u) == 0;
-    hipLaunchKernelGGL(dev::k_deliver_copy, dim3(blocks), dim3(dev::kDlCopyBlock), 0, st, static_cast<const uint8_t *>(d_img),
-                       window * WTP_MAX_PAYLOAD, vec, P, hdr, reinterpret_cast<uint8_t *>(first - ph), ph);
-    wtp_set_kernel_("k_deliver_copy");
-    return launch_check("k_deliver_copy");
+    return launch("k_deliver_copy", dev::k_deliver_copy, dim3(blocks), dim3(dev::kDlCopyBlock), st,
+                  static_cast<const uint8_t *>(d_img), window * WTP_MAX_PAYLOAD, vec, w.P, w.hdr,
+                  reinterpret_cast<uint8_t *>(first - ph), ph);
 }

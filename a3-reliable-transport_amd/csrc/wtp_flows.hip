@@ -262,11 +262,16 @@ k_flows_ack_emit(const uint8_t *__restrict__ ring, uint64_t stride, const uint32
 
 namespace {
 
-int null_arg(const char *name) { return wtp::fail(WTP_EINVAL, "null pointer: %s", name); }
+// d_work of wtp_rx_build_acks_flows: blk[ceil(n / 1024)].
+struct AckFlowsWork {
+    uint32_t *blk;
+    size_t bytes;
+};
 
-// d_work of wtp_rx_build_acks_flows, from align4 on: blk[ceil(n / 1024)].
-size_t ack_flows_bytes(size_t n) {
-    return wtp::kWorkSlack + (n + wtp::dev::kFlowBlock - 1) / wtp::dev::kFlowBlock * 4;
+AckFlowsWork ack_flows_layout(void *d_work, size_t n) {
+    wtp::Work l(d_work, 4);
+    uint32_t *blk = l.take<uint32_t>((n + wtp::dev::kFlowBlock - 1) / wtp::dev::kFlowBlock);
+    return {blk, l.bytes()};
 }
 
 }  // namespace
@@ -279,11 +284,8 @@ extern "C" int wtp_accept_data_packets_flows(const void *d_dgrams, size_t stride
     int rc = check_batch(n);
     if (rc) return rc;
     if ((rc = check_stride(stride))) return rc;
-    if (nflows > WTP_RX_MAX_FLOWS) return fail(WTP_EINVAL, "nflows %u > %u", nflows, WTP_RX_MAX_FLOWS);
-    if (window > WTP_RX_MAX_WINDOW) return fail(WTP_EINVAL, "window %u > %u", window, WTP_RX_MAX_WINDOW);
+    if ((rc = check_flows(nflows, window))) return rc;
     const uint64_t slots = uint64_t(nflows) * window;
-    if (slots > WTP_RX_MAX_FLOW_SLOTS)
-        return fail(WTP_EINVAL, "nflows %u * window %u > %u slots", nflows, window, WTP_RX_MAX_FLOW_SLOTS);
     if (n > 0) {
         if (!d_dgrams) return null_arg("d_dgrams");
         if (!d_recv_len) return null_arg("d_recv_len");
@@ -304,22 +306,20 @@ extern "C" int wtp_accept_data_packets_flows(const void *d_dgrams, size_t stride
     {
         const uint64_t lanes = std::max<uint64_t>(n, d_ack ? nflows : 0);
         const uint64_t blocks = std::max<uint64_t>(1, (lanes + 255) / 256);
-        hipLaunchKernelGGL(dev::k_flows_claim, dim3(unsigned(blocks)), dim3(256), 0, st, ring, uint64_t(stride),
-                           d_recv_len, d_ok, d_flow, uint64_t(n), d_seq0, nflows, window, d_slot_len, d_ack);
-        if ((rc = launch_check("k_flows_claim"))) return rc;
+        rc = launch("k_flows_claim", dev::k_flows_claim, dim3(unsigned(blocks)), dim3(256), st, ring, uint64_t(stride),
+                    d_recv_len, d_ok, d_flow, uint64_t(n), d_seq0, nflows, window, d_slot_len, d_ack);
+        if (rc) return rc;
     }
     // one 16-lane group per datagram; at least enough lanes to scan a small state at once
     const uint64_t scan = d_ack ? std::min<uint64_t>((slots + 255) / 256, 1024) : 0;
     const uint64_t blocks = std::max<uint64_t>({1, (uint64_t(n) * dev::kFlowGroup + 255) / 256, scan});
-    hipLaunchKernelGGL(dev::k_flows_place, dim3(unsigned(blocks)), dim3(256), 0, st, ring, uint64_t(stride),
-                       d_recv_len, d_ok, d_flow, uint64_t(n), d_seq0, nflows, window, static_cast<uint8_t *>(d_out),
-                       d_slot_len, d_place, d_ack);
-    wtp_set_kernel_("k_flows_place");
-    return launch_check("k_flows_place");
+    return launch("k_flows_place", dev::k_flows_place, dim3(unsigned(blocks)), dim3(256), st, ring, uint64_t(stride),
+                  d_recv_len, d_ok, d_flow, uint64_t(n), d_seq0, nflows, window, static_cast<uint8_t *>(d_out), d_slot_len,
+                  d_place, d_ack);
 }
 
 extern "C" size_t wtp_rx_ack_flows_work_bytes(size_t n) {
-    return ack_flows_bytes(std::min<size_t>(n, WTP_RX_MAX_BATCH));
+    return ack_flows_layout(nullptr, std::min<size_t>(n, WTP_RX_MAX_BATCH)).bytes;
 }
 
 extern "C" int wtp_rx_build_acks_flows(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len,
@@ -336,8 +336,8 @@ extern "C" int wtp_rx_build_acks_flows(const void *d_dgrams, size_t stride, cons
     if (cum && window > WTP_RX_MAX_WINDOW) return fail(WTP_EINVAL, "window %u > %u", window, WTP_RX_MAX_WINDOW);
     if ((rc = check_stride(stride))) return rc;
     if (ack_stride < 16) return fail(WTP_EINVAL, "ack_stride %zu < 16", ack_stride);
-    const size_t need = ack_flows_bytes(n);
-    if (work_bytes < need) return fail(WTP_EINVAL, "work_bytes %zu < %zu", work_bytes, need);
+    const AckFlowsWork w = ack_flows_layout(d_work, n);
+    if ((rc = check_work_bytes(work_bytes, w.bytes))) return rc;
     if (!d_counts) return null_arg("d_counts");
     if (!d_work) return null_arg("d_work");
     if (n > 0) {
@@ -351,17 +351,14 @@ extern "C" int wtp_rx_build_acks_flows(const void *d_dgrams, size_t stride, cons
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint8_t *ring = static_cast<const uint8_t *>(d_dgrams);
-    uint32_t *blk = reinterpret_cast<uint32_t *>(align4(d_work));
     const uint32_t n32 = uint32_t(n), nblk = uint32_t((n + dev::kFlowBlock - 1) / dev::kFlowBlock);
     if (n > 0) {
-        hipLaunchKernelGGL(dev::k_flows_ack_mark, dim3(nblk), dim3(dev::kFlowBlock), 0, st, ring, uint64_t(stride),
-                           d_recv_len, d_ok, d_flow, n32, d_seq0, nflows, window, blk);
-        if ((rc = launch_check("k_flows_ack_mark"))) return rc;
+        rc = launch("k_flows_ack_mark", dev::k_flows_ack_mark, dim3(nblk), dim3(dev::kFlowBlock), st, ring, uint64_t(stride),
+                    d_recv_len, d_ok, d_flow, n32, d_seq0, nflows, window, w.blk);
+        if (rc) return rc;
     }
     // n == 0: one block, which only writes d_counts = {0, 0}
-    hipLaunchKernelGGL(dev::k_flows_ack_emit, dim3(std::max(nblk, 1u)), dim3(dev::kFlowBlock), 0, st, ring,
-                       uint64_t(stride), d_recv_len, d_ok, d_flow, n32, mode, d_seq0, nflows, window, d_flow_ack, blk,
-                       nblk, static_cast<uint8_t *>(d_ack_wire), uint64_t(ack_stride), skip, max_acks, d_src, d_counts);
-    wtp_set_kernel_("k_flows_ack_emit");
-    return launch_check("k_flows_ack_emit");
+    return launch("k_flows_ack_emit", dev::k_flows_ack_emit, dim3(std::max(nblk, 1u)), dim3(dev::kFlowBlock), st, ring,
+                  uint64_t(stride), d_recv_len, d_ok, d_flow, n32, mode, d_seq0, nflows, window, d_flow_ack, w.blk, nblk,
+                  static_cast<uint8_t *>(d_ack_wire), uint64_t(ack_stride), skip, max_acks, d_src, d_counts);
 }

@@ -74,8 +74,6 @@ constexpr uint32_t kFfAdvVecs = (WTP_MAX_PAYLOAD / 16 + kFfGroup - 1) / kFfGroup
 static_assert(WTP_MAX_PAYLOAD % 16 == 0, "every slot of a 16-B aligned image is 16-B aligned");
 static_assert(uint64_t(WTP_RX_MAX_FLOW_SLOTS) + WTP_RX_MAX_WINDOW < (uint64_t(1) << 32), "a source slot fits 32 bits");
 
-typedef uint32_t ff_u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // a 16-B load of dword alignment
-
 __device__ __forceinline__ uint64_t ff_min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 
 __device__ __forceinline__ uint64_t ff_shfl_up64(uint64_t v, uint32_t d) {
@@ -303,14 +301,6 @@ k_dflows_out(uint32_t nflows, uint32_t max_slots, uint64_t stream_off, const uin
     info[4 * uint64_t(f) + 3] = Q[end > R ? end : R] - Q[R];
 }
 
-// Orders a wave's LDS stores before its later LDS loads of other lanes' data (and the
-// reverse); a wave's DS instructions execute in order, so this binds only the compiler.
-__device__ __forceinline__ void ff_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // The last index in [lo, hi] whose p is <= b (p(lo) <= b is the caller's).
 template <class Get>
 __device__ __forceinline__ uint32_t ff_owner(Get p, uint32_t lo, uint32_t hi, uint32_t b) {
@@ -341,12 +331,6 @@ __device__ __forceinline__ uint32_t ff_owner_wave(const uint64_t *__restrict__ Q
     return lo;
 }
 
-// Bytes [0, n) of a 16-byte vector as masks of its low and high half.
-__device__ __forceinline__ uint64_t ff_below_lo(uint32_t n) { return n >= 8 ? ~uint64_t(0) : (uint64_t(1) << (8 * n)) - 1; }
-__device__ __forceinline__ uint64_t ff_below_hi(uint32_t n) {
-    return n <= 8 ? 0 : n >= 16 ? ~uint64_t(0) : (uint64_t(1) << (8 * (n - 8))) - 1;
-}
-
 // Delivered bytes [b0, b1) of the round (relative to its first record's Q), b1 - b0 <= 16, as
 // bytes [skip, skip + b1 - b0) of a vector, piece by piece: a piece is what one record gives to
 // the vector, from one widened load of the 16 source bytes that put it at its place (the bytes
@@ -371,7 +355,7 @@ __device__ __forceinline__ u32x4 ff_merge(const uint8_t *__restrict__ img, uint6
         const uint64_t a = s - sh;
         uint64_t vlo = 0, vhi = 0;
         if (vec && x >= pos && a + (sh ? 20u : 16u) <= img_bytes) {
-            const u32x4 d = *reinterpret_cast<const ff_u32x4_a4 *>(img + a);
+            const u32x4 d = *reinterpret_cast<const u32x4_a4 *>(img + a);
             const uint32_t e = *reinterpret_cast<const uint32_t *>(img + a + (sh ? 16 : 12));
             vlo = (uint64_t(__builtin_amdgcn_alignbyte(d.z, d.y, sh)) << 32) | __builtin_amdgcn_alignbyte(d.y, d.x, sh);
             vhi = (uint64_t(__builtin_amdgcn_alignbyte(e, d.w, sh)) << 32) | __builtin_amdgcn_alignbyte(d.w, d.z, sh);
@@ -385,8 +369,8 @@ __device__ __forceinline__ u32x4 ff_merge(const uint8_t *__restrict__ img, uint6
                     vhi |= byte << (8 * (pos + k - 8));
             }
         }
-        lo |= vlo & ff_below_lo(pos + nb) & ~ff_below_lo(pos);
-        hi |= vhi & ff_below_hi(pos + nb) & ~ff_below_hi(pos);
+        lo |= vlo & below_lo(pos + nb) & ~below_lo(pos);
+        hi |= vhi & below_hi(pos + nb) & ~below_hi(pos);
         j = end;
     }
     u32x4 r;
@@ -425,7 +409,7 @@ k_dflows_copy(const uint8_t *__restrict__ img, uint64_t img_bytes, uint32_t vec,
                 s_P[wv][i] = uint32_t(Q[olo + i] - base);
                 if (i + 1 < cnt) s_M[wv][i] = map[olo + i];
             }
-        ff_wave_sync();
+        wave_sync();
         // the round over p(i) and m(i): from LDS, or from memory (two bodies: one address space each)
         auto body = [&](auto p, auto m) {
         uint32_t b0[kFfVecs], b1[kFfVecs], own[kFfVecs], sh[kFfVecs];
@@ -459,7 +443,7 @@ k_dflows_copy(const uint8_t *__restrict__ img, uint64_t img_bytes, uint32_t vec,
         for (uint32_t u = 0; u < kFfVecs; ++u)
             if (fast[u]) {
                 const uint8_t *q = img + soff[u];  // the dword that holds the first byte
-                d[u] = *reinterpret_cast<const ff_u32x4_a4 *>(q);
+                d[u] = *reinterpret_cast<const u32x4_a4 *>(q);
                 e[u] = *reinterpret_cast<const uint32_t *>(q + (sh[u] ? 16 : 12));  // sh == 0: d.w again, unused
             }
         uint32_t slow = 0;  // the vectors that are not one whole load: one after the other, in one body
@@ -505,7 +489,7 @@ k_dflows_copy(const uint8_t *__restrict__ img, uint64_t img_bytes, uint32_t vec,
             body([&](uint32_t i) { return sp[i - olo]; }, [&](uint32_t i) { return sm[i - olo]; });
         else
             body([&](uint32_t i) { return uint32_t(Q[i] - base); }, [&](uint32_t i) { return map[i]; });
-        ff_wave_sync();  // the next round's LDS stores follow these loads
+        wave_sync();  // the next round's LDS stores follow these loads
     }
 }
 
@@ -582,48 +566,36 @@ namespace {
 // d_work of wtp_rx_deliver_flows, from the first 16-B boundary on: hdr[2] = {K, Q_K} (u64),
 // bsum[nblk] (4 x u32), Q[slots + 1] (u64), bpre_q[nblk] (u64), flow_q[nflows] (u64),
 // map[slots], bpre_c[nblk], run[nflows], first[nflows] (u32).
-constexpr size_t kFfSlack = 16;
 struct DflowsWork {
     uint32_t nblk;
-    size_t hdr, bsum, Q, bpre_q, flow_q, map, bpre_c, run, first, bytes;
+    uint64_t *hdr, *Q, *bpre_q, *flow_q;
+    wtp::dev::u32x4 *bsum;
+    uint32_t *map, *bpre_c, *run, *first;
+    size_t bytes;
 };
 
-DflowsWork dflows_layout(uint32_t nflows, uint32_t slots) {
+DflowsWork dflows_layout(void *d_work, uint32_t nflows, uint32_t slots) {
     DflowsWork w;
+    wtp::Work l(d_work, 16);
     w.nblk = (slots + wtp::dev::kFfBlock - 1) / wtp::dev::kFfBlock;
-    w.hdr = 0;
-    w.bsum = 16;
-    w.Q = w.bsum + size_t(w.nblk) * 16;
-    w.bpre_q = w.Q + (size_t(slots) + 1) * 8;
-    w.flow_q = w.bpre_q + size_t(w.nblk) * 8;
-    w.map = w.flow_q + size_t(nflows) * 8;
-    w.bpre_c = w.map + size_t(slots) * 4;
-    w.run = w.bpre_c + size_t(w.nblk) * 4;
-    w.first = w.run + size_t(nflows) * 4;
-    w.bytes = kFfSlack + w.first + size_t(nflows) * 4;
+    w.hdr = l.take<uint64_t>(2);
+    w.bsum = l.take<wtp::dev::u32x4>(w.nblk);
+    w.Q = l.take<uint64_t>(size_t(slots) + 1);
+    w.bpre_q = l.take<uint64_t>(w.nblk);
+    w.flow_q = l.take<uint64_t>(nflows);
+    w.map = l.take<uint32_t>(slots);
+    w.bpre_c = l.take<uint32_t>(w.nblk);
+    w.run = l.take<uint32_t>(nflows);
+    w.first = l.take<uint32_t>(nflows);
+    w.bytes = l.bytes();
     return w;
-}
-
-int check_flows(uint32_t nflows, uint32_t window) {
-    using namespace wtp;
-    if (nflows > WTP_RX_MAX_FLOWS) return fail(WTP_EINVAL, "nflows %u > %u", nflows, WTP_RX_MAX_FLOWS);
-    if (window > WTP_RX_MAX_WINDOW) return fail(WTP_EINVAL, "window %u > %u", window, WTP_RX_MAX_WINDOW);
-    if (uint64_t(nflows) * window > WTP_RX_MAX_FLOW_SLOTS)
-        return fail(WTP_EINVAL, "nflows %u * window %u > %u slots", nflows, window, WTP_RX_MAX_FLOW_SLOTS);
-    return WTP_OK;
-}
-
-// [p, p + bytes) and [q, q + bytes) share a byte (bytes > 0)
-bool overlap(const void *p, const void *q, uint64_t bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(p), y = reinterpret_cast<uintptr_t>(q);
-    return x < y ? y - x < bytes : x - y < bytes;
 }
 
 }  // namespace
 
 extern "C" size_t wtp_rx_deliver_flows_work_bytes(uint32_t nflows, uint32_t window) {
     const uint32_t f = std::min<uint32_t>(nflows, WTP_RX_MAX_FLOWS), w = std::min<uint32_t>(window, WTP_RX_MAX_WINDOW);
-    return dflows_layout(f, uint32_t(std::min<uint64_t>(uint64_t(f) * w, WTP_RX_MAX_FLOW_SLOTS))).bytes;
+    return dflows_layout(nullptr, f, uint32_t(std::min<uint64_t>(uint64_t(f) * w, WTP_RX_MAX_FLOW_SLOTS))).bytes;
 }
 
 extern "C" int wtp_rx_deliver_flows(const void *d_img, const uint32_t *d_slot_len, uint32_t nflows, uint32_t window,
@@ -637,10 +609,10 @@ extern "C" int wtp_rx_deliver_flows(const void *d_img, const uint32_t *d_slot_le
     if (stream_off > stream_bytes)
         return fail(WTP_EINVAL, "stream_off %llu > stream_bytes %zu", static_cast<unsigned long long>(stream_off), stream_bytes);
     const uint32_t slots = nflows * window;
-    const DflowsWork w = dflows_layout(nflows, slots);
-    if (work_bytes < w.bytes) return fail(WTP_EINVAL, "work_bytes %zu < %zu", work_bytes, w.bytes);
-    if (!d_counts) return fail(WTP_EINVAL, "null pointer: d_counts");
-    if (!d_work) return fail(WTP_EINVAL, "null pointer: d_work");
+    const DflowsWork w = dflows_layout(d_work, nflows, slots);
+    if ((rc = check_work_bytes(work_bytes, w.bytes))) return rc;
+    if (!d_counts) return null_arg("d_counts");
+    if (!d_work) return null_arg("d_work");
     if (nflows > 0 && !d_flow_adv) return fail(WTP_EINVAL, "null pointer: d_flow_adv with nflows %u", nflows);
     if (slots > 0) {
         if (!d_img) return fail(WTP_EINVAL, "null pointer: d_img with %u slots", slots);
@@ -649,45 +621,33 @@ extern "C" int wtp_rx_deliver_flows(const void *d_img, const uint32_t *d_slot_le
             return fail(WTP_EINVAL, "null pointer: d_stream with %u slots and max_slots %u", slots, max_slots);
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    uint8_t *work = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(d_work) + 15) & ~uintptr_t(15));
-    uint64_t *hdr = reinterpret_cast<uint64_t *>(work + w.hdr);
-    dev::u32x4 *bsum = reinterpret_cast<dev::u32x4 *>(work + w.bsum);
-    uint64_t *Q = reinterpret_cast<uint64_t *>(work + w.Q);
-    uint64_t *bpre_q = reinterpret_cast<uint64_t *>(work + w.bpre_q);
-    uint64_t *flow_q = reinterpret_cast<uint64_t *>(work + w.flow_q);
-    uint32_t *map = reinterpret_cast<uint32_t *>(work + w.map);
-    uint32_t *bpre_c = reinterpret_cast<uint32_t *>(work + w.bpre_c);
-    uint32_t *run = reinterpret_cast<uint32_t *>(work + w.run);
-    uint32_t *first = reinterpret_cast<uint32_t *>(work + w.first);
     const uint64_t room = uint64_t(stream_bytes) - stream_off;
     const unsigned fblocks = (nflows + 255) / 256;
     if (nflows > 0) {
-        hipLaunchKernelGGL(dev::k_dflows_init, dim3(fblocks), dim3(256), 0, st, nflows, window, run, first, flow_q);
-        if ((rc = launch_check("k_dflows_init"))) return rc;
+        rc = launch("k_dflows_init", dev::k_dflows_init, dim3(fblocks), dim3(256), st, nflows, window, w.run, w.first, w.flow_q);
+        if (rc) return rc;
     }
     if (slots > 0) {
-        hipLaunchKernelGGL(dev::k_dflows_run, dim3((slots + 255) / 256), dim3(256), 0, st, d_slot_len, slots, window, run);
-        if ((rc = launch_check("k_dflows_run"))) return rc;
-        hipLaunchKernelGGL(dev::k_dflows_bsum, dim3(w.nblk), dim3(dev::kFfBlock), 0, st, d_slot_len, run, slots, window,
-                           max_slots, bsum);
-        if ((rc = launch_check("k_dflows_bsum"))) return rc;
+        rc = launch("k_dflows_run", dev::k_dflows_run, dim3((slots + 255) / 256), dim3(256), st, d_slot_len, slots, window, w.run);
+        if (rc) return rc;
+        rc = launch("k_dflows_bsum", dev::k_dflows_bsum, dim3(w.nblk), dim3(dev::kFfBlock), st, d_slot_len, w.run, slots, window,
+                    max_slots, w.bsum);
+        if (rc) return rc;
     }
     // no slots: the one block only writes d_counts = {0, 0, 0, 0}
-    hipLaunchKernelGGL(dev::k_dflows_mid, dim3(1), dim3(dev::kFfBlock), 0, st, bsum, w.nblk, room, bpre_c, bpre_q, Q, hdr,
-                       d_counts);
-    wtp_set_kernel_("k_dflows_mid");
-    if ((rc = launch_check("k_dflows_mid"))) return rc;
+    rc = launch("k_dflows_mid", dev::k_dflows_mid, dim3(1), dim3(dev::kFfBlock), st, w.bsum, w.nblk, room, w.bpre_c, w.bpre_q,
+                w.Q, w.hdr, d_counts);
+    if (rc) return rc;
     if (slots > 0) {
-        hipLaunchKernelGGL(dev::k_dflows_scan, dim3(w.nblk), dim3(dev::kFfBlock), 0, st, d_slot_len, run, slots, window,
-                           max_slots, stream_off, room, bpre_c, bpre_q, map, Q, first, flow_q, hdr, d_offsets_out,
-                           d_lengths_out, d_counts);
-        if ((rc = launch_check("k_dflows_scan"))) return rc;
+        rc = launch("k_dflows_scan", dev::k_dflows_scan, dim3(w.nblk), dim3(dev::kFfBlock), st, d_slot_len, w.run, slots, window,
+                    max_slots, stream_off, room, w.bpre_c, w.bpre_q, w.map, w.Q, w.first, w.flow_q, w.hdr, d_offsets_out,
+                    d_lengths_out, d_counts);
+        if (rc) return rc;
     }
     if (nflows > 0) {
-        hipLaunchKernelGGL(dev::k_dflows_out, dim3(fblocks), dim3(256), 0, st, nflows, max_slots, stream_off, run, first,
-                           flow_q, Q, hdr, d_flow_adv, d_flow_info);
-        wtp_set_kernel_("k_dflows_out");
-        if ((rc = launch_check("k_dflows_out"))) return rc;
+        rc = launch("k_dflows_out", dev::k_dflows_out, dim3(fblocks), dim3(256), st, nflows, max_slots, stream_off, w.run,
+                    w.first, w.flow_q, w.Q, w.hdr, d_flow_adv, d_flow_info);
+        if (rc) return rc;
     }
     if (slots == 0 || max_slots == 0) return WTP_OK;
     // the grid from what the arguments allow, never from d_counts: min(window, max_slots) full
@@ -698,10 +658,9 @@ extern "C" int wtp_rx_deliver_flows(const void *d_img, const uint32_t *d_slot_le
     const uint64_t per = 16 * dev::kFfRound * dev::kFfCopyWaves;
     const unsigned blocks = unsigned(std::min<uint64_t>((most + per - 1) / per, dev::kFfMaxBlocks));
     const uint32_t vec = (reinterpret_cast<uintptr_t>(d_img) & 3u) == 0;
-    hipLaunchKernelGGL(dev::k_dflows_copy, dim3(blocks), dim3(dev::kFfCopyBlock), 0, st, static_cast<const uint8_t *>(d_img),
-                       uint64_t(slots) * WTP_MAX_PAYLOAD, vec, Q, map, hdr, reinterpret_cast<uint8_t *>(dst0 - ph), ph);
-    wtp_set_kernel_("k_dflows_copy");
-    return launch_check("k_dflows_copy");
+    return launch("k_dflows_copy", dev::k_dflows_copy, dim3(blocks), dim3(dev::kFfCopyBlock), st,
+                  static_cast<const uint8_t *>(d_img), uint64_t(slots) * WTP_MAX_PAYLOAD, vec, w.Q, w.map, w.hdr,
+                  reinterpret_cast<uint8_t *>(dst0 - ph), ph);
 }
 
 extern "C" int wtp_rx_advance_flows(const void *d_img, const uint32_t *d_slot_len, uint32_t nflows, uint32_t window,
@@ -730,9 +689,7 @@ extern "C" int wtp_rx_advance_flows(const void *d_img, const uint32_t *d_slot_le
     const uint32_t groups = ((slots + 63) / 64 + 3) / 4;
     const unsigned blocks = std::min(groups, dev::kFfMaxBlocks);
     const uint32_t vec = ((reinterpret_cast<uintptr_t>(d_img) | reinterpret_cast<uintptr_t>(d_img_next)) & 15u) == 0;
-    hipLaunchKernelGGL(dev::k_rx_advance_flows, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const uint8_t *>(d_img), d_slot_len, slots, window, d_flow_adv, d_seq0,
-                       static_cast<uint8_t *>(d_img_next), d_slot_len_next, d_seq0_next, vec);
-    wtp_set_kernel_("k_rx_advance_flows");
-    return launch_check("k_rx_advance_flows");
+    return launch("k_rx_advance_flows", dev::k_rx_advance_flows, dim3(blocks), dim3(256), static_cast<hipStream_t>(stream),
+                  static_cast<const uint8_t *>(d_img), d_slot_len, slots, window, d_flow_adv, d_seq0,
+                  static_cast<uint8_t *>(d_img_next), d_slot_len_next, d_seq0_next, vec);
 }

@@ -58,8 +58,7 @@
 #include <algorithm>
 
 #include "crc32_combine.hpp"
-#include "crc32_math.hpp"
-#include "wtp_common.hpp"
+#include "wtp_crc_dev.hpp"
 
 namespace wtp {
 namespace dev {
@@ -72,21 +71,7 @@ constexpr uint32_t kTxSeg = kTxVecs * 16;  // a lane's contiguous segment: 96 B 
 static_assert(kTxSeg * (kTxGroup - 1) < WTP_MAX_PAYLOAD && kTxSeg * kTxGroup >= WTP_MAX_PAYLOAD, "segments");
 constexpr uint32_t kTxScan = 16;     // slots per lane and round of k_tx_window's scan
 
-// Slice-by-4 tables built at compile time for the device: t[0] is the byte table of
-// crc32_math.hpp's Sarwate, t[k][b] = the register after byte b and k zero bytes.
-struct TxTable {
-    uint32_t t[4][256];
-    constexpr TxTable() : t{} {
-        for (uint32_t b = 0; b < 256; ++b) {
-            uint32_t c = b;
-            for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ kPoly : (c >> 1);
-            t[0][b] = c;
-        }
-        for (int k = 1; k < 4; ++k)
-            for (uint32_t b = 0; b < 256; ++b) t[k][b] = (t[k - 1][b] >> 8) ^ t[0][t[k - 1][b] & 0xFFu];
-    }
-};
-__device__ const TxTable g_tx_table{};
+__device__ const SliceTable g_tx_table{};  // this unit's own object of the shared type (wtp_crc_dev.hpp)
 
 // x^(8 * bytes after segment g) of a full 1456-B chunk
 struct TxTail {
@@ -278,11 +263,6 @@ k_tx_select(const uint32_t *__restrict__ acked, uint32_t *sent, uint32_t infligh
 
 // ---- retransmit emit ---------------------------------------------------------------------
 
-__device__ __forceinline__ uint32_t tx_crc_word(const uint32_t *tab, uint32_t c, uint32_t w) {
-    c ^= w;
-    return tab[768 + (c & 0xFFu)] ^ tab[512 + ((c >> 8) & 0xFFu)] ^ tab[256 + ((c >> 16) & 0xFFu)] ^ tab[c >> 24];
-}
-
 __global__ void __launch_bounds__(256)
 k_tx_emit(const uint8_t *__restrict__ pay, uint64_t total_bytes, uint32_t seq0, const uint32_t *__restrict__ picked,
           const uint32_t *__restrict__ counts, uint32_t max_sel, uint8_t *__restrict__ wire, uint64_t stride,
@@ -319,10 +299,10 @@ k_tx_emit(const uint8_t *__restrict__ pay, uint64_t total_bytes, uint32_t seq0, 
 #pragma unroll
         for (uint32_t r = 0; r < kTxVecs; ++r)
             if (r == 0 || nv == kTxVecs) {
-                c = tx_crc_word(tab, c, v[r].x);
-                c = tx_crc_word(tab, c, v[r].y);
-                c = tx_crc_word(tab, c, v[r].z);
-                c = tx_crc_word(tab, c, v[r].w);
+                c = crc_word(tab, c, v[r].x);
+                c = crc_word(tab, c, v[r].y);
+                c = crc_word(tab, c, v[r].z);
+                c = crc_word(tab, c, v[r].w);
             }
     } else {
         // a short chunk, or any other alignment: bytes (exact; no access wider than the
@@ -363,21 +343,38 @@ int tx_emit_var_launch(const void *d_base, size_t base_bytes, const uint64_t *d_
 
 namespace {
 
-// d_work of wtp_tx_build_retransmit, from align4 on: picked[m], blk[blocks];
-// m = min(max_sel, inflight) entries (no more can be due).
+// d_work of wtp_tx_build_retransmit: picked[m], blk[blocks]; m = min(max_sel, inflight)
+// entries (no more can be due).
 struct TxWork {
     uint32_t m, blocks;
-    size_t picked, blk, bytes;
+    uint32_t *picked, *blk;
+    size_t bytes;
 };
 
-TxWork tx_layout(uint32_t inflight, uint32_t max_sel) {
+TxWork tx_layout(void *d_work, uint32_t inflight, uint32_t max_sel) {
     TxWork w;
+    wtp::Work l(d_work, 4);
     w.m = std::min(inflight, max_sel);
     w.blocks = (inflight + wtp::dev::kTxBlock - 1) / wtp::dev::kTxBlock;
-    w.picked = 0;
-    w.blk = size_t(w.m) * 4;
-    w.bytes = wtp::kWorkSlack + w.blk + size_t(w.blocks) * 4;
+    w.picked = l.take<uint32_t>(w.m);
+    w.blk = l.take<uint32_t>(w.blocks);
+    w.bytes = l.bytes();
     return w;
+}
+
+// The ordered selection of both retransmit calls: w.picked and d_counts, after their checks.
+int tx_select(const TxWork &w, uint32_t inflight, const uint32_t *d_acked, uint32_t *d_sent_ms, uint32_t now_ms,
+              uint32_t timeout_ms, uint32_t flags, uint32_t *d_sel, uint32_t *d_counts, hipStream_t st) {
+    using namespace wtp;
+    int rc = WTP_OK;
+    if (w.blocks > 0) {
+        if ((rc = launch("k_tx_count", dev::k_tx_count, dim3(w.blocks), dim3(dev::kTxBlock), st, d_acked, d_sent_ms, inflight,
+                         now_ms, timeout_ms, flags, w.blk)))
+            return rc;
+    }
+    // inflight == 0: one block, which only writes d_counts = {0, 0}
+    return launch("k_tx_select", dev::k_tx_select, dim3(std::max(w.blocks, 1u)), dim3(dev::kTxBlock), st, d_acked, d_sent_ms,
+                  inflight, now_ms, timeout_ms, flags, w.blk, w.blocks, w.m, d_sel, w.picked, d_counts);
 }
 
 }  // namespace
@@ -397,24 +394,20 @@ extern "C" int wtp_tx_ingest_acks(const void *d_dgrams, size_t stride, const uin
     if (e != hipSuccess) return fail(WTP_EHIP, "hipMemsetAsync(d_counts): %s", hipGetErrorString(e));
     if (n > 0 || mode == WTP_ACK_SELECTIVE) {  // n == 0: one block, which only sets d_counts[0]
         const uint64_t blocks = std::max<uint64_t>(1, (uint64_t(n) + 255) / 256);
-        hipLaunchKernelGGL(dev::k_tx_ingest, dim3(unsigned(blocks)), dim3(256), 0, st,
-                           static_cast<const uint8_t *>(d_dgrams), uint64_t(stride), d_recv_len, uint64_t(n), mode, seq0,
-                           inflight, d_acked, d_ok, d_hit, d_counts);
-        if ((rc = launch_check("k_tx_ingest"))) return rc;
+        if ((rc = launch("k_tx_ingest", dev::k_tx_ingest, dim3(unsigned(blocks)), dim3(256), st,
+                         static_cast<const uint8_t *>(d_dgrams), uint64_t(stride), d_recv_len, uint64_t(n), mode, seq0,
+                         inflight, d_acked, d_ok, d_hit, d_counts)))
+            return rc;
     }
     if (mode == WTP_ACK_SELECTIVE) {
         const uint64_t blocks = std::min<uint64_t>(std::max<uint64_t>(1, (uint64_t(inflight) + 255) / 256), 1024);
-        hipLaunchKernelGGL(dev::k_tx_lead, dim3(unsigned(blocks)), dim3(256), 0, st, inflight, d_acked, d_counts);
-        wtp_set_kernel_("k_tx_lead");
-        return launch_check("k_tx_lead");
+        return launch("k_tx_lead", dev::k_tx_lead, dim3(unsigned(blocks)), dim3(256), st, inflight, d_acked, d_counts);
     }
-    hipLaunchKernelGGL(dev::k_tx_window, dim3(1), dim3(dev::kTxBlock), 0, st, mode, inflight, d_acked, d_counts);
-    wtp_set_kernel_("k_tx_window");
-    return launch_check("k_tx_window");
+    return launch("k_tx_window", dev::k_tx_window, dim3(1), dim3(dev::kTxBlock), st, mode, inflight, d_acked, d_counts);
 }
 
 extern "C" size_t wtp_tx_work_bytes(uint32_t inflight, uint32_t max_sel) {
-    return tx_layout(std::min<uint32_t>(inflight, WTP_TX_MAX_INFLIGHT), max_sel).bytes;
+    return tx_layout(nullptr, std::min<uint32_t>(inflight, WTP_TX_MAX_INFLIGHT), max_sel).bytes;
 }
 
 extern "C" int wtp_tx_build_retransmit(const void *d_payloads, size_t total_bytes, uint32_t seq0, uint32_t inflight,
@@ -427,32 +420,18 @@ extern "C" int wtp_tx_build_retransmit(const void *d_payloads, size_t total_byte
     if (inflight > WTP_TX_MAX_INFLIGHT) return fail(WTP_EINVAL, "inflight %u > %u", inflight, WTP_TX_MAX_INFLIGHT);
     if (inflight > 0 && uint64_t(inflight - 1) * WTP_MAX_PAYLOAD >= total_bytes)
         return fail(WTP_EINVAL, "total_bytes %zu does not reach slot %u", total_bytes, inflight - 1);
-    const TxWork w = tx_layout(inflight, max_sel);
-    if (work_bytes < w.bytes) return fail(WTP_EINVAL, "work_bytes %zu < %zu", work_bytes, w.bytes);
+    const TxWork w = tx_layout(d_work, inflight, max_sel);
+    int rc = check_work_bytes(work_bytes, w.bytes);
+    if (rc) return rc;
     if (!d_counts || !d_work) return fail(WTP_EINVAL, "null pointer");
     if (inflight > 0 && (!d_payloads || !d_acked || !d_sent_ms)) return fail(WTP_EINVAL, "null pointer");
     if (w.m > 0 && !d_wire) return fail(WTP_EINVAL, "null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    uint8_t *work = align4(d_work);
-    uint32_t *picked = reinterpret_cast<uint32_t *>(work + w.picked);
-    uint32_t *blk = reinterpret_cast<uint32_t *>(work + w.blk);
-    int rc = WTP_OK;
-    if (w.blocks > 0) {
-        hipLaunchKernelGGL(dev::k_tx_count, dim3(w.blocks), dim3(dev::kTxBlock), 0, st, d_acked, d_sent_ms, inflight,
-                           now_ms, timeout_ms, flags, blk);
-        if ((rc = launch_check("k_tx_count"))) return rc;
-    }
-    // inflight == 0: one block, which only writes d_counts = {0, 0}
-    hipLaunchKernelGGL(dev::k_tx_select, dim3(std::max(w.blocks, 1u)), dim3(dev::kTxBlock), 0, st, d_acked, d_sent_ms,
-                       inflight, now_ms, timeout_ms, flags, blk, w.blocks, w.m, d_sel, picked, d_counts);
-    wtp_set_kernel_("k_tx_select");
-    if ((rc = launch_check("k_tx_select")) || w.m == 0) return rc;
+    if ((rc = tx_select(w, inflight, d_acked, d_sent_ms, now_ms, timeout_ms, flags, d_sel, d_counts, st)) || w.m == 0) return rc;
     const uint64_t blocks = (uint64_t(w.m) * dev::kTxGroup + 255) / 256;
-    hipLaunchKernelGGL(dev::k_tx_emit, dim3(unsigned(blocks)), dim3(256), 0, st, static_cast<const uint8_t *>(d_payloads),
-                       uint64_t(total_bytes), seq0, picked, d_counts, w.m, static_cast<uint8_t *>(d_wire), uint64_t(wire_stride),
-                       d_wire_len);
-    wtp_set_kernel_("k_tx_emit");
-    return launch_check("k_tx_emit");
+    return launch("k_tx_emit", dev::k_tx_emit, dim3(unsigned(blocks)), dim3(256), st, static_cast<const uint8_t *>(d_payloads),
+                  uint64_t(total_bytes), seq0, w.picked, d_counts, w.m, static_cast<uint8_t *>(d_wire), uint64_t(wire_stride),
+                  d_wire_len);
 }
 
 extern "C" int wtp_tx_build_retransmit_var(const void *d_base, size_t base_bytes, const uint64_t *d_offsets,
@@ -464,27 +443,15 @@ extern "C" int wtp_tx_build_retransmit_var(const void *d_base, size_t base_bytes
     using namespace wtp;
     if (wire_stride < WTP_HEADER_BYTES + WTP_MAX_PAYLOAD) return fail(WTP_EINVAL, "wire_stride %zu < 1472", wire_stride);
     if (inflight > WTP_TX_MAX_INFLIGHT) return fail(WTP_EINVAL, "inflight %u > %u", inflight, WTP_TX_MAX_INFLIGHT);
-    const TxWork w = tx_layout(inflight, max_sel);
-    if (work_bytes < w.bytes) return fail(WTP_EINVAL, "work_bytes %zu < %zu", work_bytes, w.bytes);
-    if (!d_counts || !d_work) return fail(WTP_EINVAL, "null pointer: d_counts or d_work");
+    const TxWork w = tx_layout(d_work, inflight, max_sel);
+    int rc = check_work_bytes(work_bytes, w.bytes);
+    if (rc) return rc;
+    if (!d_counts || !d_work) return null_arg("d_counts or d_work");
     if (inflight > 0 && (!d_base || !d_offsets || !d_lengths || !d_acked || !d_sent_ms))
-        return fail(WTP_EINVAL, "null pointer: d_base, d_offsets, d_lengths, d_acked or d_sent_ms");
-    if (w.m > 0 && !d_wire) return fail(WTP_EINVAL, "null pointer: d_wire");
+        return null_arg("d_base, d_offsets, d_lengths, d_acked or d_sent_ms");
+    if (w.m > 0 && !d_wire) return null_arg("d_wire");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    uint8_t *work = align4(d_work);
-    uint32_t *picked = reinterpret_cast<uint32_t *>(work + w.picked);
-    uint32_t *blk = reinterpret_cast<uint32_t *>(work + w.blk);
-    int rc = WTP_OK;
-    if (w.blocks > 0) {
-        hipLaunchKernelGGL(dev::k_tx_count, dim3(w.blocks), dim3(dev::kTxBlock), 0, st, d_acked, d_sent_ms, inflight,
-                           now_ms, timeout_ms, flags, blk);
-        if ((rc = launch_check("k_tx_count"))) return rc;
-    }
-    // inflight == 0: one block, which only writes d_counts = {0, 0}
-    hipLaunchKernelGGL(dev::k_tx_select, dim3(std::max(w.blocks, 1u)), dim3(dev::kTxBlock), 0, st, d_acked, d_sent_ms,
-                       inflight, now_ms, timeout_ms, flags, blk, w.blocks, w.m, d_sel, picked, d_counts);
-    wtp_set_kernel_("k_tx_select");
-    if ((rc = launch_check("k_tx_select")) || w.m == 0) return rc;
-    return tx_emit_var_launch(d_base, base_bytes, d_offsets, d_lengths, seq0, picked, d_counts, w.m, d_wire, wire_stride,
+    if ((rc = tx_select(w, inflight, d_acked, d_sent_ms, now_ms, timeout_ms, flags, d_sel, d_counts, st)) || w.m == 0) return rc;
+    return tx_emit_var_launch(d_base, base_bytes, d_offsets, d_lengths, seq0, w.picked, d_counts, w.m, d_wire, wire_stride,
                               d_wire_len, d_crc_out, st);
 }

@@ -34,8 +34,7 @@
 #include <algorithm>
 
 #include "crc32_combine.hpp"
-#include "crc32_math.hpp"
-#include "wtp_common.hpp"
+#include "wtp_crc_dev.hpp"
 
 namespace wtp {
 namespace dev {
@@ -47,22 +46,7 @@ constexpr uint32_t kTvPiece = 16 * kTvVecs;             // a lane's contiguous b
 constexpr uint32_t kTvMaxPieces = (WTP_MAX_PAYLOAD + kTvPiece - 1) / kTvPiece;  // 23
 constexpr uint32_t kTvMaxBlocks = 1280;                 // the capped grid: 5 workgroups per CU (96 VGPRs, 27 KB LDS)
 
-// Slice-by-4 tables built at compile time for the device (as wtp_tx.hip's and
-// wtp_buildvar.hip's): t[0] is the byte table of crc32_math.hpp's Sarwate, t[k][b] = the
-// register after byte b and k zero bytes.
-struct TvTable {
-    uint32_t t[4][256];
-    constexpr TvTable() : t{} {
-        for (uint32_t b = 0; b < 256; ++b) {
-            uint32_t c = b;
-            for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ kPoly : (c >> 1);
-            t[0][b] = c;
-        }
-        for (int k = 1; k < 4; ++k)
-            for (uint32_t b = 0; b < 256; ++b) t[k][b] = (t[k - 1][b] >> 8) ^ t[0][t[k - 1][b] & 0xFFu];
-    }
-};
-__device__ const TvTable g_tv_table{};
+__device__ const SliceTable g_tv_table{};  // this unit's own object of the shared type (wtp_crc_dev.hpp)
 
 // One table, so that a workgroup fills it with one load per lane: v[k] = x^(8 * kTvPiece * k), k
 // whole pieces after a piece, k < kTvMaxPieces; v[kTvMaxPieces + r] = x^(8 * r), r <= kTvPiece
@@ -82,74 +66,6 @@ __device__ const TvPow g_tv_pow{};
 static_assert(TvPow{}.v[kTvMaxPieces + kTvPiece] == gf::xpow8(kTvPiece) &&
                   TvPow{}.v[kTvMaxPieces - 1] == gf::xpow8(kTvPiece * (kTvMaxPieces - 1)) && kTvPows <= kTvBlock,
               "powers");
-
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // a 16-B load of dword alignment
-
-__device__ __forceinline__ uint32_t tv_crc_word(const uint32_t *tab, uint32_t c, uint32_t w) {
-    c ^= w;
-    return tab[768 + (c & 0xFFu)] ^ tab[512 + ((c >> 8) & 0xFFu)] ^ tab[256 + ((c >> 16) & 0xFFu)] ^ tab[c >> 24];
-}
-
-// The register after bytes [0, nb) of v (little-endian byte order, nb <= 16) from c.
-__device__ __forceinline__ uint32_t tv_crc_vec(const uint32_t *tab, uint32_t c, u32x4 v, uint32_t nb) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (uint32_t r = 0; r < 4; ++r) {
-        if (nb >= 4 * r + 4) {
-            c = tv_crc_word(tab, c, w[r]);
-        } else if (nb > 4 * r) {
-#pragma unroll
-            for (uint32_t q = 0; q < 3; ++q)
-                if (4 * r + q < nb) c = tab[(c ^ (w[r] >> (8 * q))) & 0xFFu] ^ (c >> 8);
-        }
-    }
-    return c;
-}
-
-// Bytes [from, nb) of v to d, one by one.
-__device__ __forceinline__ void tv_store_bytes(uint8_t *d, u32x4 v, uint32_t from, uint32_t nb) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (uint32_t b = 0; b < 16; ++b)
-        if (b >= from && b < nb) d[b] = uint8_t(w[b / 4] >> (8 * (b % 4)));
-}
-
-// Bytes [0, nb) of v to d, nb <= 16.  vec: d is 16-B aligned.
-__device__ __forceinline__ void tv_store_vec(uint8_t *d, u32x4 v, uint32_t nb, bool vec) {
-    if (vec && nb == 16) {
-        *reinterpret_cast<u32x4 *>(d) = v;
-    } else if (vec) {
-        uint32_t *dw = reinterpret_cast<uint32_t *>(d);
-        if (nb >= 4) dw[0] = v.x;
-        if (nb >= 8) dw[1] = v.y;
-        if (nb >= 12) dw[2] = v.z;
-        tv_store_bytes(d, v, nb & ~3u, nb);
-    } else {
-        tv_store_bytes(d, v, 0, nb);
-    }
-}
-
-// Payload bytes [src, src + nb), nb <= 16, as a vector, loaded one by one.
-__device__ __forceinline__ u32x4 tv_load_bytes(const uint8_t *src, uint32_t nb) {
-    uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (uint32_t b = 0; b < 16; ++b)
-        if (b < nb) w[b / 4] |= uint32_t(src[b]) << (8 * (b % 4));
-    u32x4 v;
-    v.x = w[0];
-    v.y = w[1];
-    v.z = w[2];
-    v.w = w[3];
-    return v;
-}
-
-// Orders a wave's LDS stores before its later LDS loads of other lanes' data (and the
-// reverse); a wave's DS instructions execute in order, so this binds only the compiler.
-__device__ __forceinline__ void tv_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Datagram k < min(counts[0], max_sel) is record picked[k] and fills wire slot k.
 __global__ void __launch_bounds__(kTvBlock, 5)  // five waves per SIMD: the capped grid is five workgroups per CU
@@ -207,7 +123,7 @@ k_tx_emit_var(const uint8_t *__restrict__ base, uint64_t base_bytes, const uint6
         s_hi[wv][lane] = uint32_t(off >> 32);
         s_len[wv][lane] = len;
         s_acc[wv][lane] = 0;
-        tv_wave_sync();
+        wave_sync();
         for (uint32_t task0 = 0; task0 < total; task0 += 64) {
             // this lane's piece: its owner is the first datagram whose pieces end after `task`
             const uint32_t task = task0 + lane;
@@ -262,12 +178,12 @@ k_tx_emit_var(const uint8_t *__restrict__ base, uint64_t base_bytes, const uint6
                 v.z = __builtin_amdgcn_alignbyte(d[u].w, d[u].z, shv[u]);
                 v.w = __builtin_amdgcn_alignbyte(e[u], d[u].w, shv[u]);
                 // within 20 bytes of an edge of the buffer: the payload's own bytes, one by one
-                if (nbv[u] && !fast[u]) v = tv_load_bytes(sp[u], nbv[u]);
-                if (nbv[u]) tv_store_vec(dp[u], v, nbv[u], vec);
+                if (nbv[u] && !fast[u]) v = load_bytes(sp[u], nbv[u]);
+                if (nbv[u]) store_vec(dp[u], v, nbv[u], vec);
                 // piece P = 16u + lane / 4 of the wave, vector m, in slot (m + P / 4) % 4 of its 64 bytes
                 s_move[wv][4 * (16 * u + lane / 4) + ((m + lane / 16) & 3u)] = v;
             }
-            tv_wave_sync();
+            wave_sync();
             // the hash: a lane's own piece, its vectors in order; init ~0 enters with the
             // payload's first piece, xorout ~0 at the owner
             uint32_t c = q == 0 ? 0xFFFFFFFFu : 0u;
@@ -277,21 +193,21 @@ k_tx_emit_var(const uint8_t *__restrict__ base, uint64_t base_bytes, const uint6
             for (uint32_t k = 0; k < kTvVecs; ++k) {
                 const u32x4 v = s_move[wv][4 * lane + ((k + lane / 4) & 3u)];
                 if (k < nfull) {
-                    c = tv_crc_word(tab, c, v.x);
-                    c = tv_crc_word(tab, c, v.y);
-                    c = tv_crc_word(tab, c, v.z);
-                    c = tv_crc_word(tab, c, v.w);
+                    c = crc_word(tab, c, v.x);
+                    c = crc_word(tab, c, v.y);
+                    c = crc_word(tab, c, v.z);
+                    c = crc_word(tab, c, v.w);
                 }
                 if (k == nfull) part = v;
             }
-            if (nbytes & 15u) c = tv_crc_vec(tab, c, part, nbytes & 15u);
+            if (nbytes & 15u) c = crc_vec(tab, c, part, nbytes & 15u);
             if (mine) {
                 if (q + 1 == onp)
                     s_last[wv][o] = c;
                 else
                     atomicXor(&s_acc[wv][o], gf::mul(c, ppiece[onp - 2 - q]));
             }
-            tv_wave_sync();  // the next turn's s_move stores follow these loads
+            wave_sync();  // the next turn's s_move stores follow these loads
         }
         if (has) {
             uint32_t crc = 0;
@@ -302,7 +218,7 @@ k_tx_emit_var(const uint8_t *__restrict__ base, uint64_t base_bytes, const uint6
                 if (vec)
                     *reinterpret_cast<u32x4 *>(slot) = h;
                 else
-                    tv_store_bytes(slot, h, 0, 16);
+                    store_bytes(slot, h, 0, 16);
             }
             if (wire_len) wire_len[i] = valid ? WTP_HEADER_BYTES + len : 0;
             if (crc_out) crc_out[i] = crc;
@@ -317,11 +233,9 @@ int tx_emit_var_launch(const void *d_base, size_t base_bytes, const uint64_t *d_
                        size_t wire_stride, uint32_t *d_wire_len, uint32_t *d_crc_out, hipStream_t st) {
     const uint32_t vec = (reinterpret_cast<uintptr_t>(d_wire) & 15u) == 0 && wire_stride % 16 == 0;
     const unsigned blocks = std::min((m + dev::kTvWaves - 1) / dev::kTvWaves, dev::kTvMaxBlocks);
-    hipLaunchKernelGGL(dev::k_tx_emit_var, dim3(blocks), dim3(dev::kTvBlock), 0, st, static_cast<const uint8_t *>(d_base),
-                       uint64_t(base_bytes), d_offsets, d_lengths, m, seq0, picked, d_counts,
-                       static_cast<uint8_t *>(d_wire), uint64_t(wire_stride), vec, d_wire_len, d_crc_out);
-    wtp_set_kernel_("k_tx_emit_var");
-    return launch_check("k_tx_emit_var");
+    return launch("k_tx_emit_var", dev::k_tx_emit_var, dim3(blocks), dim3(dev::kTvBlock), st, static_cast<const uint8_t *>(d_base),
+                  uint64_t(base_bytes), d_offsets, d_lengths, m, seq0, picked, d_counts, static_cast<uint8_t *>(d_wire),
+                  uint64_t(wire_stride), vec, d_wire_len, d_crc_out);
 }
 
 }  // namespace wtp

@@ -36,7 +36,7 @@ class WtpError(RuntimeError):
     pass
 
 
-def _load() -> C.CDLL:
+def _load() -> tuple:
     if not os.path.exists(LIB_PATH):
         raise WtpError(f"HIP library not built: {LIB_PATH} (run `make -C a3-reliable-transport_amd lib` "
                        "or __graft_entry__.build())")
@@ -95,21 +95,10 @@ def _load() -> C.CDLL:
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args
-    return lib
+    return lib, tuple(sig)
 
 
-LIB = _load()
-EXPORTED = ("wtp_version", "wtp_last_error", "wtp_last_kernel", "wtp_device_count", "wtp_init", "wtp_device_status", "wtp_reserve_cus", "wtp_crc32",
-            "wtp_crc32_batch_fixed", "wtp_crc32_batch_var", "wtp_crc32_batch_packed", "wtp_crc32_verify_batch", "wtp_build_data_packets",
-            "wtp_build_data_packets_var", "wtp_accept_data_packets", "wtp_tx_ingest_acks", "wtp_tx_work_bytes", "wtp_tx_build_retransmit",
-            "wtp_tx_build_retransmit_var", "wtp_rx_ack_work_bytes", "wtp_rx_build_acks", "wtp_rx_deliver_work_bytes", "wtp_rx_deliver",
-            "wtp_rx_advance", "wtp_tx_advance",
-            "wtp_accept_data_packets_flows", "wtp_rx_ack_flows_work_bytes", "wtp_rx_build_acks_flows",
-            "wtp_rx_deliver_flows_work_bytes", "wtp_rx_deliver_flows", "wtp_rx_advance_flows",
-            "wtp_crc32_combine", "wtp_crc32_concat_work_bytes", "wtp_crc32_concat", "wtp_crc32_buffer_work_bytes",
-            "wtp_crc32_buffer", "wtp_crc32_host_buffer",
-            "wtp_crc32_host_batch_fixed", "wtp_crc32_host_chunked", "wtp_crc32_host_chunked_multi", "wtp_crc32_host_verify",
-            "wtp_host_build_data_packets", "wtp_host_alloc", "wtp_host_free", "wtp_synth_fill")
+LIB, EXPORTED = _load()  # EXPORTED: the names of the signature table, in its order
 
 
 def _check(rc: int, what: str) -> None:
