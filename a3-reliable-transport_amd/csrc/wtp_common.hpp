@@ -99,6 +99,14 @@ inline int check_flows(uint32_t nflows, uint32_t window) {
         return fail(WTP_EINVAL, "nflows %u * window %u > %u slots", nflows, window, WTP_RX_MAX_FLOW_SLOTS);
     return WTP_OK;
 }
+// the multi-connection sender state: the same split of one d_acked / d_sent_ms among the flows
+inline int check_tx_flows(uint32_t nflows, uint32_t window) {
+    if (nflows > WTP_TX_MAX_FLOWS) return fail(WTP_EINVAL, "nflows %u > %u", nflows, WTP_TX_MAX_FLOWS);
+    if (window > WTP_TX_MAX_INFLIGHT) return fail(WTP_EINVAL, "window %u > %u", window, WTP_TX_MAX_INFLIGHT);
+    if (uint64_t(nflows) * window > WTP_TX_MAX_FLOW_SLOTS)
+        return fail(WTP_EINVAL, "nflows %u * window %u > %u slots", nflows, window, WTP_TX_MAX_FLOW_SLOTS);
+    return WTP_OK;
+}
 // [p, p + bytes) and [q, q + bytes) share a byte (bytes > 0)
 inline bool overlap(const void *p, const void *q, uint64_t bytes) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(p), y = reinterpret_cast<uintptr_t>(q);

@@ -1,4 +1,4 @@
-// wtp_crc_dev.hpp — what the DATA builders (wtp_tx.hip, wtp_buildvar.hip, wtp_txvar.hip) share
+// wtp_crc_dev.hpp — what the DATA builders (wtp_tx.hip, wtp_buildvar.hip, wtp_txvar.hip, wtp_tx_flows.hip) share
 // on the device: the slice-by-4 table's type and the byte helpers around a 16-B vector.  Each
 // unit defines its own table object and keeps its kernel bodies.  Internal.
 #pragma once

@@ -30,6 +30,8 @@ RX_MAX_WINDOW = 1 << 20       # WTP_RX_MAX_WINDOW (cumulative mode of rx_build_a
 RX_MAX_BATCH = 1 << 24        # WTP_RX_MAX_BATCH
 RX_MAX_FLOWS = 1 << 20        # WTP_RX_MAX_FLOWS
 RX_MAX_FLOW_SLOTS = 1 << 24   # WTP_RX_MAX_FLOW_SLOTS (nflows * window of accept_data_packets_flows)
+TX_MAX_FLOWS = 1 << 20        # WTP_TX_MAX_FLOWS
+TX_MAX_FLOW_SLOTS = 1 << 20   # WTP_TX_MAX_FLOW_SLOTS (nflows * window of the tx_*_flows calls)
 
 
 class WtpError(RuntimeError):
@@ -76,6 +78,10 @@ def _load() -> tuple:
         "wtp_rx_deliver_flows_work_bytes": (sz, [u32, u32]),
         "wtp_rx_deliver_flows": (i32, [vp, vp, u32, u32, u32, vp, sz, u64, vp, vp, vp, vp, vp, vp, sz, vp]),
         "wtp_rx_advance_flows": (i32, [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "wtp_tx_ingest_acks_flows": (i32, [vp, sz, vp, vp, sz, u32, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "wtp_tx_advance_flows": (i32, [vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "wtp_tx_build_retransmit_var_flows": (i32, [vp, sz, vp, vp, sz, vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, sz,
+                                                    u32, vp, vp, vp, vp, vp, sz, vp]),
         "wtp_crc32_combine": (u32, [u32, u32, u64]),
         "wtp_crc32_concat_work_bytes": (sz, [sz]),
         "wtp_crc32_concat": (i32, [vp, vp, u64, u64, sz, vp, sz, vp, vp]),
@@ -341,6 +347,51 @@ def rx_advance_flows(img, slot_len, nflows: int, window: int, flow_adv, seq0, im
     _check(LIB.wtp_rx_advance_flows(_dptr(img), _dptr(slot_len), nflows, window, _dptr(flow_adv), _dptr(seq0),
                                     _dptr(img_next), _dptr(slot_len_next), _dptr(seq0_next), _stream(stream)),
            "wtp_rx_advance_flows")
+
+
+# ---- the multi-connection sender -----------------------------------------------------------
+def tx_ingest_acks_flows(dgrams, stride: int, recv_len, flow, n: int, mode: int, seq0, rec0, rec_end, nflows: int,
+                         window: int, acked, ok, hit=None, flow_adv=None, flow_fresh=None, stream=None) -> None:
+    """tx_ingest_acks for the interleaved ACKs of many connections (wtp_tx_ingest_acks_flows):
+    `flow` (n x u32) names each datagram's connection (>= nflows: none); `seq0`, `rec0`,
+    `rec_end` (nflows x u32, device) are each flow's seqNum and record index of slot 0 and
+    one past its last record, so its window holds min(window, rec_end - rec0) slots.  Flow f
+    owns entries [f*window, (f+1)*window) of `acked`; `hit` (n x u32) is the slot or `a` within
+    the flow; flow_adv / flow_fresh (nflows x u32) = each flow's leading ACKed run and the
+    slots newly ACKed."""
+    _check(LIB.wtp_tx_ingest_acks_flows(_dptr(dgrams), stride, _dptr(recv_len), _dptr(flow), n, mode, _dptr(seq0),
+                                        _dptr(rec0), _dptr(rec_end), nflows, window, _dptr(acked), _dptr(ok), _dptr(hit),
+                                        _dptr(flow_adv), _dptr(flow_fresh), _stream(stream)), "wtp_tx_ingest_acks_flows")
+
+
+def tx_advance_flows(acked, sent_ms, nflows: int, window: int, flow_adv, fill_ms: int, seq0, rec0, acked_next,
+                     sent_ms_next, seq0_next, rec0_next, stream=None) -> None:
+    """tx_advance for every flow in one launch (wtp_tx_advance_flows): flow f's entries of
+    `acked` / `sent_ms` move down by min(flow_adv[f], window) into `acked_next` /
+    `sent_ms_next`, 0 / fill_ms behind them, and seq0_next[f] / rec0_next[f] = seq0[f] /
+    rec0[f] + that (u32 device tensors; flow_adv is tx_ingest_acks_flows' as it is).  The four
+    base arrays may all be None: then the bases do not move."""
+    _check(LIB.wtp_tx_advance_flows(_dptr(acked), _dptr(sent_ms), nflows, window, _dptr(flow_adv), fill_ms & 0xFFFFFFFF,
+                                    _dptr(seq0), _dptr(rec0), _dptr(acked_next), _dptr(sent_ms_next), _dptr(seq0_next),
+                                    _dptr(rec0_next), _stream(stream)), "wtp_tx_advance_flows")
+
+
+def tx_build_retransmit_var_flows(base, base_bytes: int, offsets, lengths, nrec: int, seq0, rec0, rec_end, nflows: int,
+                                  window: int, acked, sent_ms, now_ms: int, timeout_ms: int, flags: int, wire,
+                                  wire_stride: int, max_sel: int, sel=None, wire_len=None, crc_out=None, counts=None,
+                                  work=None, stream=None) -> None:
+    """tx_build_retransmit_var over every flow's window (wtp_tx_build_retransmit_var_flows): slot
+    (f, s) is record rec0[f] + s of the one table (base, offsets, lengths; nrec entries) and
+    carries seqNum seq0[f] + s.  The due slots of all flows, flow 0's first, become the entries
+    of one ring; sel[k] = f*window + s names entry k's slot (its peer is flow sel[k] // window);
+    wire_len / crc_out (u32) are 0 for an invalid record; counts (2 x u32) = (emitted, due).
+    The scratch is tx_work_bytes(nflows * window, max_sel)."""
+    work, wp, wb = _work(work, tx_work_bytes(min(nflows * window, TX_MAX_FLOW_SLOTS), max_sel))
+    _check(LIB.wtp_tx_build_retransmit_var_flows(_dptr(base), base_bytes, _dptr(offsets), _dptr(lengths), nrec, _dptr(seq0),
+                                                 _dptr(rec0), _dptr(rec_end), nflows, window, _dptr(acked), _dptr(sent_ms),
+                                                 now_ms & 0xFFFFFFFF, timeout_ms, flags, _dptr(wire), wire_stride, max_sel,
+                                                 _dptr(sel), _dptr(wire_len), _dptr(crc_out), _dptr(counts), wp, wb,
+                                                 _stream(stream)), "wtp_tx_build_retransmit_var_flows")
 
 
 # ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------

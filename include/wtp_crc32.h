@@ -760,6 +760,138 @@ int wtp_tx_advance(const uint32_t *d_acked, const uint32_t *d_sent_ms, uint32_t 
                    const uint32_t *d_adv, uint32_t fill_ms,
                    uint32_t *d_acked_next, uint32_t *d_sent_ms_next, void *stream);
 
+/* ---- the multi-connection sender: ingest, slide and rebuild every flow at once ---------
+   The sender's side of the multi-flow round: wtp_tx_ingest_acks_flows -> wtp_tx_advance_flows
+   -> wtp_tx_build_retransmit_var_flows, three calls whatever the number of connections, all
+   stream-ordered, with the window bases moved on the device, so one captured graph serves
+   every round.  Per-connection semantics are exactly those of wtp_tx_ingest_acks,
+   wtp_tx_advance and wtp_tx_build_retransmit_var; only the batching across connections, and
+   the bases living in device memory, are new.
+
+   State.  All flows share one `window`.  Flow f owns global slots [f*window, (f+1)*window) of
+   one d_acked[S] and one d_sent_ms[S], S = nflows*window; the global slot of (f, s) is g =
+   f*window + s.  Limits: nflows <= WTP_TX_MAX_FLOWS, window <= WTP_TX_MAX_INFLIGHT and S (in
+   64 bits) <= WTP_TX_MAX_FLOW_SLOTS (the one-level block ranking of the selection holds one
+   count per lane of a 1024-lane block; a ring of 2^20 datagrams is already 1.5 GiB of wire).
+   All flows' records sit in one table (d_base, base_bytes, d_offsets[nrec], d_lengths[nrec]),
+   wtp_build_data_packets_var's layout.  Three per-flow device arrays are read when the
+   kernels run, never when the call is made: d_seq0[f] = the seqNum of the flow's slot 0,
+   d_rec0[f] = the table index of the record in slot 0, d_rec_end[f] = one past the flow's
+   last record (constant over a transfer).  Slot (f, s) is record d_rec0[f] + s, and the
+   flow's window holds inflight_f = min(window, d_rec_end[f] - d_rec0[f]) slots if d_rec_end[f]
+   > d_rec0[f], else 0.  All three calls compute it the same way, so every input is defined;
+   slots [inflight_f, window) of a flow are never read as window state and never counted.
+
+   wtp_tx_ingest_acks_flows takes one batch with the ACKs of all connections in arrival
+   order; d_flow[i] names the datagram's flow and any value >= nflows means "no connection".
+   For every f the result is what wtp_tx_ingest_acks gives on the subsequence d_flow[i] == f,
+   in index order, with seq0 = d_seq0[f], inflight = inflight_f and the flow's sub-array of
+   d_acked; d_flow_adv[f] and d_flow_fresh[f] are that call's d_counts[0] (the leading ACKed
+   run) and d_counts[1] (the slots that went 0 -> 1).  d_ok[i] is written for every datagram
+   by wtp_tx_ingest_acks' rule, whatever its flow; d_hit[i] is the slot (selective) or a
+   (cumulative) within the flow, WTP_NOT_PLACED for every datagram that does not count and
+   for "no connection"; d_hit may be NULL.  In cumulative mode a flow's slots [0, the largest
+   a of that flow) are filled.  d_flow_adv and d_flow_fresh are written for every f < nflows,
+   also with n == 0 and for a flow no datagram names; n == 0, nflows == 0 and window == 0 are
+   valid.  Nothing else in d_acked changes; every other input is only read.  nflows == 1
+   reproduces wtp_tx_ingest_acks word for word.
+   WTP_EINVAL (before any device is touched, each with its own message): n >= 2^31, an unknown
+   mode, stride < 16, a limit exceeded, a NULL d_flow_adv or d_flow_fresh with nflows > 0, a
+   NULL d_seq0, d_rec0 or d_rec_end with nflows > 0, a NULL d_acked with S > 0, a NULL
+   d_dgrams, d_recv_len, d_flow or d_ok with n > 0.
+   No scratch: the two per-flow arrays are the only accumulators.  Stream-ordered launches
+   (selective: per-flow init, one lane per datagram, one pass over the S slots; cumulative:
+   init, datagrams, the fill over the S slots, the leading run over the S slots, a per-flow
+   pass), no host synchronisation, no library table, so no wtp_init is needed before a
+   capture.  Nothing is serial per flow: 2^20 flows of one slot and one flow of 2^20 slots
+   are the same work. */
+#define WTP_TX_MAX_FLOWS      (1u << 20)
+#define WTP_TX_MAX_FLOW_SLOTS (1u << 20)   /* nflows * window; equals WTP_TX_MAX_INFLIGHT */
+int wtp_tx_ingest_acks_flows(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len,
+                             const uint32_t *d_flow, size_t n, uint32_t mode,
+                             const uint32_t *d_seq0, const uint32_t *d_rec0, const uint32_t *d_rec_end,
+                             uint32_t nflows, uint32_t window, uint32_t *d_acked,
+                             uint8_t *d_ok, uint32_t *d_hit,
+                             uint32_t *d_flow_adv, uint32_t *d_flow_fresh, void *stream);
+
+/* wtp_tx_advance_flows slides every flow's sub-window and bases: wtp_tx_advance per flow with
+   slots = window and a_f = min(d_flow_adv[f], window), read on the device when the kernel
+   runs (wtp_tx_ingest_acks_flows' d_flow_adv passes as it is), in one launch with one lane per
+   global slot.  For every flow and s < window with t = s + a_f: d_acked_next[f*window + s] =
+   d_acked[f*window + t] if t < window, else 0, and d_sent_ms_next[f*window + s] =
+   d_sent_ms[f*window + t] if t < window, else fill_ms (wtp_tx_advance's rule: with fill_ms =
+   now_ms - timeout_ms - 1 the entries shifted in are due at the next build).  d_seq0_next[f] =
+   d_seq0[f] + a_f and d_rec0_next[f] = d_rec0[f] + a_f, both mod 2^32: the next round's calls
+   read the bases where this call left them.  d_seq0, d_rec0, d_seq0_next and d_rec0_next may
+   be NULL all together; then the bases do not move.  The inputs are only read and nothing
+   outside the four output arrays is written.  S == 0 is valid, launches nothing and writes
+   nothing.  nflows == 1 reproduces wtp_tx_advance.
+   WTP_EINVAL (before any device is touched, each with its own message): a limit exceeded;
+   exactly one of d_seq0 / d_seq0_next or of d_rec0 / d_rec0_next NULL, or one pair without the
+   other; with S > 0 a NULL d_flow_adv, d_acked, d_sent_ms, d_acked_next or d_sent_ms_next; an
+   output range overlapping an input range or another output range: the state arrays over 4*S
+   bytes, the base arrays (and d_flow_adv against the next bases) over 4*nflows bytes.  Ranges
+   that touch are valid.
+   One stream-ordered launch with no host synchronisation, allocation, scratch or library
+   table; wtp_last_kernel() names "k_txf_advance". */
+int wtp_tx_advance_flows(const uint32_t *d_acked, const uint32_t *d_sent_ms,
+                         uint32_t nflows, uint32_t window, const uint32_t *d_flow_adv, uint32_t fill_ms,
+                         const uint32_t *d_seq0, const uint32_t *d_rec0,
+                         uint32_t *d_acked_next, uint32_t *d_sent_ms_next,
+                         uint32_t *d_seq0_next, uint32_t *d_rec0_next, void *stream);
+
+/* wtp_tx_build_retransmit_var_flows selects the due slots of every flow and builds exactly
+   those datagrams into one ring.
+   Selection: global slot g = (f, s) is due iff s < inflight_f, d_acked[g] == 0 and (flags &
+   WTP_RETX_ALL or (uint32_t)(now_ms - d_sent_ms[g]) > timeout_ms).  Due slots are taken in
+   rising g (flow 0's first, then s rising) and the first min(due, max_sel) of them are
+   emitted: entry k gets d_sel[k] = g and d_sent_ms[g] = now_ms; the host routes ring entry k
+   to the peer of flow d_sel[k] / window.  d_counts[0] = the number emitted, d_counts[1] = the
+   number due.  The selection does not look at the records.  The cut: a ring shorter than the
+   due set cuts in flow-major order, as wtp_rx_deliver_flows cuts; the flow where the cut
+   falls emits a prefix of its due slots and every later flow emits nothing in this call.
+   With timers the caller calls again: emitted slots are no longer due, so the next call
+   takes up where this one stopped.  With WTP_RETX_ALL every call starts at flow 0 again, so
+   the ring must hold the whole due set (max_sel >= S always does) or the late flows starve.
+   Emit: entry k, with f = d_sel[k] / window, s = d_sel[k] - f*window and r = d_rec0[f] + s
+   (mod 2^32), is valid iff r < nrec and record r satisfies wtp_build_data_packets_var's rule
+   (d_lengths[r] <= WTP_MAX_PAYLOAD, d_offsets[r] <= base_bytes, d_lengths[r] <= base_bytes -
+   d_offsets[r]); no entry at or above nrec of either table is read.  A valid entry writes
+   d_wire[k*wire_stride ..) = htonl{type = 2, seqNum = d_seq0[f] + s (mod 2^32), length = len,
+   checksum = crc32(payload)} || payload, byte-identical to oracle.build_datagram and to what
+   wtp_tx_build_retransmit_var writes for that record, d_wire_len[k] = 16 + len and
+   d_crc_out[k] = the checksum.  An invalid entry leaves its slot untouched, d_wire_len[k] = 0
+   and d_crc_out[k] = 0.  Everything else is wtp_tx_build_retransmit_var's contract,
+   unchanged: entries k >= d_counts[0], bytes [16 + len, wire_stride) of every slot and the
+   timers of slots not emitted stay as they were; the record table, d_acked and the per-flow
+   arrays are only read; no byte outside [d_base, d_base + base_bytes) is loaded; d_sel,
+   d_wire_len and d_crc_out may be NULL; the fast path is a 16-B aligned d_wire with
+   wire_stride % 16 == 0 and any source alignment, and other wire alignments are built
+   bytewise, exactly.  nflows == 1 reproduces that call word for word (with its d_offsets and
+   d_lengths advanced by d_rec0[0] and inflight = inflight_0).  S == 0 and max_sel == 0 are
+   valid: d_counts is still written.
+   Scratch: work_bytes >= wtp_tx_work_bytes(nflows*window, max_sel), the existing function and
+   the existing layout, because the selection is the single-window selection over the S
+   global slots with a wider predicate; the scratch contract is wtp_tx_build_retransmit's.
+   WTP_EINVAL (before any device is touched, each with its own message): wire_stride < 1472; a
+   limit exceeded; work_bytes too small; a NULL d_counts or d_work; with S > 0 a NULL d_base,
+   d_offsets or d_lengths, a NULL d_acked or d_sent_ms, a NULL d_seq0, d_rec0 or d_rec_end; a
+   NULL d_wire with S > 0 and max_sel > 0.
+   Stream-ordered launches (count, select, emit) with no host synchronisation and no
+   allocation; grids are sized from S and max_sel, never from device values.  The call reads
+   no library table, so it needs no wtp_init before a capture; captures, replays and
+   concurrent calls on different work buffers are independent.  wtp_last_kernel() names
+   "k_txf_emit", or "k_txf_select" when S or max_sel is 0 and nothing can be emitted. */
+int wtp_tx_build_retransmit_var_flows(const void *d_base, size_t base_bytes,
+                                      const uint64_t *d_offsets, const uint32_t *d_lengths, size_t nrec,
+                                      const uint32_t *d_seq0, const uint32_t *d_rec0, const uint32_t *d_rec_end,
+                                      uint32_t nflows, uint32_t window,
+                                      const uint32_t *d_acked, uint32_t *d_sent_ms, uint32_t now_ms,
+                                      uint32_t timeout_ms, uint32_t flags,
+                                      void *d_wire, size_t wire_stride, uint32_t max_sel,
+                                      uint32_t *d_sel, uint32_t *d_wire_len, uint32_t *d_crc_out,
+                                      uint32_t *d_counts, void *d_work, size_t work_bytes, void *stream);
+
 /* ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------
    The reference's crc32(buf, size) takes any size; these give it for device-resident data
    of any size from the per-chunk CRCs, by zlib's crc32_combine identity
