@@ -2,11 +2,15 @@
 wtp_rx_build_acks_flows: every output of both calls is compared with tests/flows_model.py,
 whose accept is accept_model.accept per flow, and for one flow with the single-connection
 calls on the device.  Buffers are gpu_support's guarded ones and every output starts from a
-sentinel, so a byte or word that must stay untouched is checkable."""
+sentinel, so a byte or word that must stay untouched is checkable.
+
+Section 8 puts every payload length 0 .. 1484 once through k_flows_place, over three flows, on
+the vector path and on the bytewise one (the inputs are tests/flows_cases.py's)."""
 import numpy as np
 import pytest
 
 import accept_model
+import flows_cases as C
 import flows_model as F
 import oracle as O
 from gpu_support import W, W_noinit  # noqa: F401 (fixtures: W for verify's tables; the graph test takes W_noinit)
@@ -575,3 +579,28 @@ def test_transfer_of_four_connections(W, mode):
         W.crc32_buffer(end.file[f].t, total, crc)
         assert int(u32(crc)[0]) == O.crc32(host)
     assert_no_data_error(W)
+
+
+# ---- 8. every length through the copy -----------------------------------------------------------------------
+@pytest.mark.parametrize("stride,ring_off,out_off", [(1488, 0, 0), (1504, 0, 0), (1500, 1, 3)],
+                         ids=["vector-1488", "vector-1504", "bytewise"])
+def test_every_length(W, stride, ring_off, out_off):
+    """The counterpart of test_gpu_accept.py::test_every_length for k_flows_place, this unit's own
+    copy (16 lanes per datagram: a strided vector loop, the 1456-byte case, a tail of one byte per
+    lane): one datagram of every payload length 0 .. 1484, dealt round-robin to 3 flows of window
+    500 and shuffled.  Up to 1456 bytes are placed, with bytes [len, 1456) of the slot untouched;
+    1457 .. 1484 are intact where the ring slot holds them (a 1488-byte slot holds 1472 payload
+    bytes: the longer ones are cut by the ring and not ok) and not placed.  Aligned ring and
+    image take the vector path; ring at +1 and image at +3 the bytewise one."""
+    ring, rl, flow, seq0, order = C.accept_case(stride)
+    st = DevFlows(3, 500, out_off=out_off)
+    ok, place, out, sl, ack = st.accept(W, ring, stride, rl, flow, seq0, ring_off=ring_off)
+    assert (st.ring.t.data_ptr() + 16) % 16 == ring_off and st.img.t.data_ptr() % 16 == out_off
+    fits = order + 16 <= stride
+    assert np.array_equal(ok != 0, fits) and fits[order <= 1472].all() and (stride == 1488 or fits.all())
+    assert np.array_equal(place, np.where(order <= MAXP, order // 3, F.NOT_PLACED))
+    assert ack.tolist() == [(int(s) + a) & M32 for s, a in zip(seq0, (486, 486, 485))]
+    img = out.reshape(1500, MAXP)
+    for ln in range(MAXP + 1):
+        g = (ln % 3) * 500 + ln // 3
+        assert sl[g] == ln and (img[g, ln:] == 0xA5).all(), ln

@@ -6,10 +6,16 @@ flow with the single-connection calls on the device.
 The sentinel rule of every case: the whole stream buffer holds sentinels, and so do the guards
 around it and the regions behind every output array; the image sits between two pages of
 sentinel; all inputs are read back unchanged (the states of 2^20 slots by a sum); every
-output is compared element-wise against the model."""
+output is compared element-wise against the model.
+
+Section 11 puts every length 0 .. 1456 once through k_dflows_copy (five flows, four phases of
+the first delivered byte, an aligned and an unaligned image, a capacity cut inside a full-size
+record) and through k_rx_advance_flows (with EMPTY slots and the non-length values, a different
+advance per flow, four image pre-fills); the state is tests/flows_cases.py's."""
 import numpy as np
 import pytest
 
+import flows_cases as C
 import flows_flush_model as M
 import flows_model as F
 import oracle as O
@@ -94,14 +100,14 @@ def deliver(W, st, max_slots, cap, off, phase=0, records=True, info=True, work_o
     return want
 
 
-def advance(W, st, advs, seq0=None, images=True, next_off=0):
+def advance(W, st, advs, seq0=None, images=True, next_off=0, fill=0xEE):
     """One wtp_rx_advance_flows on the device and in the model into a sentinel-filled second
     state; asserts every output equal and every input untouched; returns the model's (image, slot_len,
     seq0) of that state."""
     nf, w, slots = st.nflows, st.window, st.slots
     h_adv = np.array(advs, dtype=np.uint64)
     adv = Words(h_adv, dtype=np.uint64)
-    nimg = Bytes(fill=0xEE, size=slots * MAXP, off=next_off, front=PAGE, back=PAGE)
+    nimg = Bytes(fill=fill, size=slots * MAXP, off=next_off, front=PAGE, back=PAGE)
     nsl = Words(SENT32, slots)
     sq, nsq = (Words(seq0), Words(SENT32, nf)) if seq0 is not None else (None, Words(SENT32, nf))
     W.rx_advance_flows(st.img.t if images else None, st.sl.t, nf, w, adv.t, sq.t if sq else None, nimg.t if images else None,
@@ -111,7 +117,7 @@ def advance(W, st, advs, seq0=None, images=True, next_off=0):
         assert W.LIB.wtp_last_kernel().decode() == "k_rx_advance_flows"
     prior_sq = np.full(nf, SENT32, np.uint32)
     w_img, w_sl, w_sq = M.advance_flows(st.h_img if images else None, st.h_sl, nf, w, h_adv, seq0,
-                                        np.full(slots * MAXP, 0xEE, np.uint8) if images else None, np.full(slots, SENT32, np.uint32),
+                                        np.full(slots * MAXP, fill, np.uint8) if images else None, np.full(slots, SENT32, np.uint32),
                                         prior_sq if seq0 is not None else None)
     assert np.array_equal(nsl.get(), w_sl)
     assert np.array_equal(nsq.get(), w_sq if seq0 is not None else prior_sq)
@@ -119,7 +125,7 @@ def advance(W, st, advs, seq0=None, images=True, next_off=0):
     if images:
         assert_bytes_equal(got_img, w_img, MAXP, lambda s: f"flow {s // max(w, 1)} slot {s % max(w, 1)}, slot_len {w_sl[s]:#x}")
     else:
-        assert (got_img == 0xEE).all()
+        assert (got_img == fill).all()
     st.check_untouched()
     assert np.array_equal(adv.get(), h_adv) and (sq is None or np.array_equal(sq.get(), np.asarray(seq0, np.uint32)))
     assert_no_data_error(W)
@@ -630,3 +636,50 @@ def test_transfer_of_four_connections(W, mode):
         W.crc32_buffer(end.file[f].t, total, crc)
         assert int(u32(crc)[0]) == O.crc32(host)
     assert_no_data_error(W)
+
+
+# ---- 11. every length through the copies -------------------------------------------------------------------
+# k_dflows_copy and k_rx_advance_flows are this unit's own copies of the single-window bodies:
+# the counterparts of test_gpu_deliver.py::test_every_length_once and
+# test_gpu_advance.py::test_every_length_once.  The state is flows_cases.flush_state's, whose
+# properties tests/test_flows_cases.py asserts on the CPU.
+FIRST_BYTE = ((0, 0), (5, 0), (3, 7), (17, 14))  # (stream_off, the buffer's phase): first bytes at 0, 5, 10, 15 mod 16
+
+
+@pytest.mark.parametrize("img_off", [0, 1], ids=["vector", "bytewise"])
+def test_every_length_once(W, img_off):
+    """5 flows x window 300 whose leading runs of 300, 290, 280, 300 and 287 slots together hold
+    every length 0 .. 1456 once, permuted: at four phases of the first delivered byte, with
+    stream_off mod 16 moving as well; then with stream_bytes ending inside the full-size record
+    in the middle of flow 2's run, so flows 3 and 4 deliver nothing."""
+    img, sl, runs = C.flush_state(img_off)
+    nf, w = C.FLUSH_FLOWS, C.FLUSH_WINDOW
+    st = State(nf, w, img, sl, img_off=img_off)
+    total = MAXP * (MAXP + 1) // 2
+    assert {(off + phase) % 16 for off, phase in FIRST_BYTE} == {0, 5, 10, 15} and len({off % 16 for off, _ in FIRST_BYTE}) == 4
+    for off, phase in FIRST_BYTE:
+        want = deliver(W, st, w, off + total + 5, off, phase=phase)
+        assert want[3].tolist() == runs.tolist() and want[5].tolist() == [MAXP + 1, MAXP + 1, total, total]
+        assert sorted(want[2][:MAXP + 1].tolist()) == list(range(MAXP + 1))
+    at = 2 * w + int(runs[2]) // 2
+    before = int(want[1][int(want[4][2][1]) + int(runs[2]) // 2]) - FIRST_BYTE[-1][0]  # the bytes in front of that record
+    assert sl[at] == MAXP
+    cut = deliver(W, st, w, 9 + before + 700, 9, phase=2)
+    assert cut[3].tolist() == [runs[0], runs[1], runs[2] // 2, 0, 0] and int(cut[5][2]) == before
+
+
+@pytest.mark.parametrize("fill", [0x00, 0xFF, 0x3C, 0xA5])
+def test_advance_every_length_once(W, fill):
+    """The same state: every length once, 40 EMPTY slots, 1457, a claim pattern and 0xFFFFFFFE,
+    moved by 0, the window, 2^40, 5 and 290 in the five flows into an image that holds `fill`: a
+    copy one byte too long shows as a changed tail byte at one of the four pre-fills.  The next
+    image is 16-B aligned for the even fills and one byte off for the odd ones."""
+    img, sl, runs = C.flush_state(fill)
+    nf, w = C.FLUSH_FLOWS, C.FLUSH_WINDOW
+    st = State(nf, w, img, sl)
+    advs = [0, w, 1 << 40, 5, 290]
+    w_img, w_sl, w_sq = advance(W, st, advs, seq0=[M32 - 2, 7, M32, 0xFFFFFFFC, 9], fill=fill, next_off=fill & 1)
+    assert w_sq.tolist() == [M32 - 2, 7 + w, w - 1, 1, 299]
+    assert np.array_equal(w_sl[:w], sl[:w]) and (w_sl[w:3 * w] == EMPTY).all() and np.array_equal(w_sl[3 * w:4 * w - 5], sl[3 * w + 5:4 * w])
+    short = np.flatnonzero(w_sl < MAXP)
+    assert short.size > 500 and all((w_img[s * MAXP + int(w_sl[s]):(s + 1) * MAXP] == fill).all() for s in short.tolist())

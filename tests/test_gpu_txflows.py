@@ -5,11 +5,24 @@ windows whose boundaries fall inside a wave and inside a 1024-slot block, an emi
 enough for a round size above one, the bytewise paths, offsets above 2^32, a sender graph
 captured once and replayed over states whose bases only the device writes, and the whole
 transfer with seven calls per round.  Every output lies between guards and is compared whole,
-and so is the state a call must not touch."""
+and so is the state a call must not touch.
+
+Section 9 gives the unit's own copies of the single-window bodies the edge suite those bodies
+have: k_txf_emit at every length 0 .. 1456 and source phase with five due patterns and four
+ring sizes on the vector and the bytewise path, on each side of every change of its round size
+(g = 0 .. 6) and with 400 000 records (a second round per wave); k_txf_count / k_txf_select at
+S = 2^20 (1024 block counts) and S = 65 537 (65) with sparse due sets and a cut inside a flow;
+txf_due across the clock's wrap, at timeout 0 and 0xFFFFFFFF, with timers in the future, with
+and without WTP_RETX_ALL; k_txf_ingest with 70 000 ACKs over some 280 workgroups and 20 000 on
+one flow; k_txf_advance by 0, 1, window - 1, window, window + 1 and 0xFFFFFFFF at windows around
+64, 256 and 1024 with wrapping bases, and at 2^20 slots.  Its inputs are tests/flows_cases.py's."""
+import functools
+
 import numpy as np
 import pytest
 
 import buildvar_model
+import flows_cases as C
 import flows_model as F
 import oracle as O
 import retx_model as R
@@ -24,9 +37,10 @@ JUNK = 0x77777777
 
 
 # ---- one call on the device and in the model -------------------------------------------------
-def ingest(W, ring, stride, rl, flow, mode, seq0, rec0, rec_end, nflows, window, acked, with_hit=True, ring_off=0):
+def ingest(W, ring, stride, rl, flow, mode, seq0, rec0, rec_end, nflows, window, acked, with_hit=True, ring_off=0,
+           model=T.ingest_flows):
     """wtp_tx_ingest_acks_flows against the model; returns the model's (ok, hit, acked, adv, fresh)."""
-    want = T.ingest_flows(ring, stride, rl, flow, mode, seq0, rec0, rec_end, nflows, window, acked)
+    want = model(ring, stride, rl, flow, mode, seq0, rec0, rec_end, nflows, window, acked)
     n = len(rl)
     d_ring = Bytes(ring if n else np.zeros(16, np.uint8), off=ring_off, front=64, back=64)
     ins = [Words(a) for a in (rl, flow, seq0, rec0, rec_end)]
@@ -45,13 +59,13 @@ def ingest(W, ring, stride, rl, flow, mode, seq0, rec0, rec_end, nflows, window,
     return want
 
 
-def advance(W, acked, sent, nflows, window, adv, fill, seq0, rec0, bases=True):
+def advance(W, acked, sent, nflows, window, adv, fill, seq0, rec0, bases=True, model=T.advance_flows):
     """wtp_tx_advance_flows into buffers that hold JUNK, against the model; returns the model's
     (acked_next, sent_next, seq0_next, rec0_next)."""
     S = nflows * window
     junk, junk_f = np.full(S, JUNK, np.uint32), np.full(nflows, JUNK, np.uint32)
-    want = T.advance_flows(acked, sent, nflows, window, adv, fill, seq0 if bases else None, rec0 if bases else None, junk, junk,
-                           junk_f if bases else None, junk_f if bases else None)
+    want = model(acked, sent, nflows, window, adv, fill, seq0 if bases else None, rec0 if bases else None, junk, junk,
+                 junk_f if bases else None, junk_f if bases else None)
     ins = [Words(a) for a in (acked, sent, adv, seq0, rec0)]
     outs = [Words(JUNK, S), Words(JUNK, S), Words(JUNK, nflows), Words(JUNK, nflows)]
     b = (lambda x: x.t) if bases else (lambda x: None)  # noqa: E731
@@ -521,4 +535,169 @@ def test_transfer_of_four_connections(W, mode):
         crc = torch.zeros(1, dtype=torch.int32, device="cuda")
         W.crc32_buffer(end.file[f].t, total, crc)
         assert int(u32(crc)[0]) == O.crc32(host)
+    assert_no_data_error(W)
+
+
+# ---- 9. the copies' edges: every length, phase, round size and scale ------------------------------------
+# The kernels of wtp_tx_flows.hip are their own copies of the single-window bodies, so the edge
+# suites of tests/test_gpu_retxvar.py and test_gpu_retx.py do not reach them.  The inputs are
+# tests/flows_cases.py's, whose preconditions tests/test_flows_cases.py asserts on the CPU; the
+# model is the loop-free path of tests/txflows_model.py, held there to the per-flow path.
+FAST = functools.partial(T.retransmit_var_flows, fast=True)
+
+
+def case_batch(c, base_off=0):
+    return Batch(c["base"], c["offs"], c["lens"], base_off=base_off, base_bytes=int(c["lens"].sum()))
+
+
+def build_case(W, b, c, sent, max_sel, now=C.NOW, timeout=C.TIMEOUT, flags=0, model=FAST, **kw):
+    return build(W, b, c["lens"].size, c["seq0"], c["rec0"], c["rec_end"], c["nflows"], c["window"], c["acked"], sent, now, timeout,
+                 flags, max_sel, model=model, **kw)
+
+
+@pytest.mark.parametrize("pattern", C.PATTERNS)
+def test_every_length_due_patterns_and_rings(W, pattern):
+    """1457 records, every length 0 .. 1456 once, permuted and packed (all 16 source phases, from
+    d_base at byte 0 and 1 of its allocation), over 5 flows x window 300 of which the last has 257
+    records and one wraps its sequence numbers; none, one, about 10 %, 50 % and all of them due;
+    rings of due, due - 1 (then the call again on the timers that call left: the one slot left),
+    due + 70 and S entries; on the vector path and on the bytewise one (wire at +1, stride 1473)."""
+    c = C.every_length_case(pattern)
+    d = c["d"]
+    for base_off in (0, 1):
+        b = case_batch(c, base_off)
+        assert b.phases() == set(range(16))
+        for wire_off, stride in ((0, STRIDE), (1, 1473)):
+            for max_sel in c["rings"]:
+                want = build_case(W, b, c, c["sent"], max_sel, wire_off=wire_off, wire_stride=stride)
+                assert want[5] == (min(d, max_sel), d)
+                if max_sel == d - 1:  # the call again: the last due slot alone, in a ring of one entry where d - 1 == 0
+                    again = build_case(W, b, c, want[4], max(d - 1, 1), wire_off=wire_off, wire_stride=stride)
+                    assert again[5] == (1, 1) and again[1][0] == np.flatnonzero(c["due"])[-1]
+    assert_no_data_error(W)
+
+
+def _count_case(W, count, rec_len, max_sel):
+    c = C.count_case(count, rec_len)
+    want = build_case(W, case_batch(c), c, c["sent"], max_sel)
+    assert want[5] == (count, count) and np.array_equal(want[1][:count], c["due"])
+
+
+@pytest.mark.parametrize("threshold", C.THRESHOLDS)
+def test_each_side_of_every_round_size_change(W, threshold):
+    """The capped grid of k_txf_emit (see flows_cases.THRESHOLDS): `threshold` datagrams run with
+    G, one more with 2 G, the due slots spread evenly over 3 windows that are no multiple of 64.
+    4-byte records at every threshold; up to 20 480 also a ring fitted to the count and full-size
+    records."""
+    for count in (threshold, threshold + 1):
+        _count_case(W, count, 4, count + 9)
+        if threshold <= 4 * C.CAP_WAVES:
+            _count_case(W, count, 4, count)
+            _count_case(W, count, MAXP, count + 9)
+    assert_no_data_error(W)
+
+
+def test_400000_short_records_all_due(W):
+    """400 000 records of at most 8 bytes over 3 flows, all due: G = 64 and 6250 rounds over 5120
+    waves, so waves run their loop a second time or leave it.  Compared on the device with the
+    builder's rings of the three flows' records (byte-identity), and on the host: the sentinel
+    tails, the headers and CRCs against the oracle, the payload bytes against the source."""
+    c = C.many_short_records()
+    n, nf, w, S = c["n"], c["nflows"], c["window"], c["S"]
+    b = case_batch(c)
+    want = torch.full((n * STRIDE,), 0xA5, dtype=torch.uint8, device="cuda")
+    for f in range(nf):
+        lo = f * w
+        W.build_data_packets_var(b.base, b.base_bytes, b.o[lo:], b.l.t[lo:], min(w, n - lo), int(c["seq0"][f]), want[lo * STRIDE:],
+                                 STRIDE)
+    whole = Bytes(fill=0xA5, size=n * STRIDE, front=64, back=64, guard=0xA5)
+    ins = [Words(c[k]) for k in ("seq0", "rec0", "rec_end")]
+    acked, sent, counts = Words(0, S), Words(C.OLD, S), Words(0x99, 2)
+    sel, wl, crc = Words(12345, n), Words(12345, n), Words(12345, n)
+    work = torch.empty(W.tx_work_bytes(S, n), dtype=torch.uint8, device="cuda")
+    W.tx_build_retransmit_var_flows(b.base, b.base_bytes, b.o, b.l.t, n, ins[0].t, ins[1].t, ins[2].t, nf, w, acked.t, sent.t, C.NOW,
+                                    C.TIMEOUT, 0, whole.t, STRIDE, n, sel.t, wl.t, crc.t, counts.t, work=work)
+    torch.cuda.synchronize()
+    assert W.LIB.wtp_last_kernel().decode() == "k_txf_emit"
+    assert torch.equal(whole.payload, want)
+    del want
+    slots = whole.payload.view(n, STRIDE)
+    assert bool((slots[:, 24:] == 0xA5).all())
+    whole.check_guards()
+    assert counts.get().tolist() == [n, n] and np.array_equal(sel.get(), np.arange(n))
+    assert np.array_equal(sent.get(), np.concatenate([np.full(n, C.NOW, np.uint32), np.full(S - n, C.OLD, np.uint32)]))
+    assert np.array_equal(wl.get(), c["lens"] + 16) and np.array_equal(crc.get(), O.batch_var(c["base"], c["offs"], c["lens"]))
+    front = slots[:, :24].cpu().numpy()
+    head = np.ascontiguousarray(front[:, :16]).view(">u4")  # the headers against the oracle
+    k = np.arange(n)
+    assert (head[:, 0] == 2).all() and np.array_equal(head[:, 1], (c["seq0"][k // w].astype(np.int64) + k % w) & M32)
+    assert np.array_equal(head[:, 2], c["lens"]) and np.array_equal(head[:, 3], crc.get())
+    at = c["offs"].astype(np.int64)[:, None] + np.arange(8)
+    inside = np.arange(8) < c["lens"][:, None]
+    assert np.array_equal(front[:, 16:][inside], c["base"][np.minimum(at, c["base"].size - 1)][inside])
+    assert (front[:, 16:][~inside] == 0xA5).all()
+    b.check_untouched()
+    assert_no_data_error(W)
+
+
+@pytest.mark.parametrize("nflows,window", C.SCALE_SHAPES)
+def test_selection_at_scale(W, nflows, window):
+    """S = 2^20 slots, the documented limit: 1024 block counts, one per lane of k_txf_select,
+    summed per wave and then over 16 waves; and S = 65 537: 65 block counts, one lane in the
+    second wave of that sum.  A sparse due set that holds global slots 0, 63, 64, 1023, 1024,
+    65 535, 65 536 and 2^20 - 1 and the first and last slot of several flows, into a ring with
+    room for all of it and into one that ends inside a flow."""
+    c = C.scale_case(nflows, window)
+    b, d = case_batch(c), c["d"]
+    full = build_case(W, b, c, c["sent"], d + 50)
+    assert full[5] == (d, d) and np.array_equal(full[1][:d], np.flatnonzero(c["due"]))
+    cut = C.cut_inside_a_flow(full[1], d, window)
+    part = build_case(W, b, c, c["sent"], cut)
+    assert part[5] == (cut, d) and np.array_equal(part[1], full[1][:cut])  # a prefix of the first call's
+    assert_no_data_error(W)
+
+
+@pytest.mark.parametrize("now,timeout", C.TIMER_CASES)
+def test_timers_clock_wrap_and_retx_all(W, now, timeout):
+    """uint32(now - sent) > timeout in every flow of three, with timers of age timeout - 1,
+    timeout, timeout + 1 and timers in the future, across the clock's wrap, at timeout 0 and
+    0xFFFFFFFF, without WTP_RETX_ALL and with it; the model is the per-flow one, and the
+    selection is also the rule's own."""
+    c = C.timer_case(now, timeout)
+    b = case_batch(c)
+    for flags, sel in ((0, c["due"]), (T.RETX_ALL, c["all"])):
+        got = build_case(W, b, c, c["sent"], c["S"], now=now, timeout=timeout, flags=flags, model=T.retransmit_var_flows)
+        assert got[5] == (sel.size, sel.size) and np.array_equal(got[1][:sel.size], sel)
+    assert_no_data_error(W)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_ack_batch_over_many_workgroups(W, mode):
+    """About 70 000 shuffled ACKs over 300 flows x window 100, some 280 workgroups of
+    k_txf_ingest: 20 000 for three slots of one flow and 20 000 of one value for another (the
+    atomics' hot spots), damaged checksums, other types, unknown flows, the sequence numbers on
+    both sides of every window, and a prior state that makes flow_fresh differ from the hits."""
+    c = C.ack_batch(mode)
+    got = ingest(W, c["ring"], 16, c["rl"], c["flow"], mode, c["seq0"], c["rec0"], c["rec_end"], c["nflows"], c["window"], c["acked0"],
+                 model=functools.partial(T.ingest_flows, fast=True))
+    C.check_ack_batch(c, got)
+    assert_no_data_error(W)
+
+
+@pytest.mark.parametrize("window", C.SLIDE_WINDOWS)
+def test_slide_by_every_kind_of_advance(W, window):
+    """7 flows whose flow_adv cycles through 0, 1, window - 1, window, window + 1 and 0xFFFFFFFF,
+    with bases that wrap 2^32 in the slide, and without the base arrays."""
+    c = C.slide_case(window)
+    got = advance(W, c["acked"], c["sent"], 7, window, c["adv"], c["fill"], c["seq0"], c["rec0"])
+    C.check_slide(c, got)
+    advance(W, c["acked"], c["sent"], 7, window, c["adv"], c["fill"], c["seq0"], c["rec0"], bases=False)
+    assert_no_data_error(W)
+
+
+def test_slide_at_the_slot_limit(W):
+    c = C.slide_case(1024, nflows=1024)
+    got = advance(W, c["acked"], c["sent"], 1024, 1024, c["adv"], c["fill"], c["seq0"], c["rec0"],
+                  model=functools.partial(T.advance_flows, fast=True))
+    C.check_slide(c, got)
     assert_no_data_error(W)

@@ -35,8 +35,16 @@ def inflight_of(rec0, rec_end, f, window):
     return min(window, e - a) if e > a else 0
 
 
-def ingest_flows(ring, stride, recv_len, flow, mode, seq0, rec0, rec_end, nflows, window, acked):
-    """Returns (ok, hit, acked, flow_adv[nflows], flow_fresh[nflows])."""
+def inflight_all(rec0, rec_end, nflows, window):
+    """inflight_of for every flow at once, as int64."""
+    a, e = np.asarray(rec0[:nflows], dtype=np.int64), np.asarray(rec_end[:nflows], dtype=np.int64)
+    return np.where(e > a, np.minimum(window, e - a), 0)
+
+
+def ingest_flows(ring, stride, recv_len, flow, mode, seq0, rec0, rec_end, nflows, window, acked, fast=False):
+    """Returns (ok, hit, acked, flow_adv[nflows], flow_fresh[nflows]).  fast: the same without a
+    loop over flows or datagrams, for batches of tens of thousands (tests/test_txflows_model.py
+    holds it to the per-flow path, which is the definition)."""
     ring = np.ascontiguousarray(ring, dtype=np.uint8)
     recv_len = np.ascontiguousarray(recv_len, dtype=np.uint32)
     flow = np.ascontiguousarray(flow, dtype=np.uint32)
@@ -44,6 +52,8 @@ def ingest_flows(ring, stride, recv_len, flow, mode, seq0, rec0, rec_end, nflows
     assert flow.size == n
     acked = np.array(acked, dtype=np.uint32, copy=True)
     ok = R.verify_limited(ring, stride, recv_len)[0]
+    if fast:
+        return (ok,) + _ingest_flows_fast(ring, stride, n, ok, flow, mode, seq0, rec0, rec_end, nflows, window, acked)
     hit = np.full(n, NOT_PLACED, dtype=np.uint32)
     adv, fresh = np.zeros(nflows, np.uint32), np.zeros(nflows, np.uint32)
     for f in range(nflows):
@@ -56,10 +66,39 @@ def ingest_flows(ring, stride, recv_len, flow, mode, seq0, rec0, rec_end, nflows
     return ok, hit, acked, adv, fresh
 
 
+def _ingest_flows_fast(ring, stride, n, ok, flow, mode, seq0, rec0, rec_end, nflows, window, acked):
+    """A batch's marks are a set of global slots (selective) or a prefix per flow (cumulative),
+    so the order of the datagrams only matters for hit, which is per datagram."""
+    S = nflows * window
+    infl = inflight_all(rec0, rec_end, nflows, window)
+    types, seqs = R.headers(ring, stride, n)
+    known = flow < nflows
+    f = np.where(known, flow, 0).astype(np.int64)
+    if nflows == 0:
+        return np.full(n, NOT_PLACED, np.uint32), acked, np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+    d = (seqs.astype(np.int64) - np.asarray(seq0, dtype=np.int64)[f]) & M32
+    counts = (ok != 0) & (types == 3) & known & ((d < infl[f]) if mode == SELECTIVE else ((d > 0) & (d <= infl[f])))
+    hit = np.where(counts, d, NOT_PLACED).astype(np.uint32)
+    slot = np.arange(S, dtype=np.int64) % max(window, 1)
+    if mode == SELECTIVE:
+        marks = np.unique(f[counts] * window + d[counts])
+    else:
+        top = np.zeros(nflows, np.int64)
+        np.maximum.at(top, f[counts], d[counts])
+        marks = np.flatnonzero(slot < np.repeat(top, window))
+    new = marks[acked[marks] == 0]
+    fresh = np.bincount(new // max(window, 1), minlength=nflows).astype(np.uint32)
+    acked[new] = 1
+    is_open = ((acked[:S] == 0) & (slot < np.repeat(infl, window))).reshape(nflows, window)
+    adv = np.where(is_open.any(axis=1), is_open.argmax(axis=1), infl) if window else np.zeros(nflows, np.int64)
+    return hit, acked, adv.astype(np.uint32), fresh
+
+
 def advance_flows(acked, sent_ms, nflows, window, flow_adv, fill_ms, seq0, rec0, acked_next, sent_ms_next, seq0_next,
-                  rec0_next):
+                  rec0_next, fast=False):
     """Returns (acked_next, sent_ms_next, seq0_next, rec0_next) after the call; the four base
-    arrays may all be None (None comes back for the two outputs)."""
+    arrays may all be None (None comes back for the two outputs).  fast: advance_model's
+    loop-free form per flow, for windows of 2^18 slots."""
     assert (seq0 is None) == (rec0 is None) == (seq0_next is None) == (rec0_next is None)
     ak = np.array(acked_next, dtype=np.uint32, copy=True)
     sm = np.array(sent_ms_next, dtype=np.uint32, copy=True)
@@ -68,20 +107,27 @@ def advance_flows(acked, sent_ms, nflows, window, flow_adv, fill_ms, seq0, rec0,
     for f in range(nflows if window else 0):  # no slots: nothing is written
         lo, hi = f * window, (f + 1) * window
         a = min(int(flow_adv[f]), window)
-        ak[lo:hi], sm[lo:hi] = V.tx_advance(acked[lo:hi], sent_ms[lo:hi], window, a, fill_ms, ak[lo:hi], sm[lo:hi])
+        one = V.tx_advance_fast if fast else V.tx_advance
+        ak[lo:hi], sm[lo:hi] = one(acked[lo:hi], sent_ms[lo:hi], window, a, fill_ms, ak[lo:hi], sm[lo:hi])
         if sq is not None:
             sq[f], rc[f] = (int(seq0[f]) + a) & M32, (int(rec0[f]) + a) & M32
     return ak, sm, sq, rc
 
 
 def retransmit_var_flows(base, base_bytes, offsets, lengths, nrec, seq0, rec0, rec_end, nflows, window, acked, sent_ms,
-                         now_ms, timeout_ms, flags, wire, wire_stride, max_sel, sel=None, wire_len=None, crc_out=None):
+                         now_ms, timeout_ms, flags, wire, wire_stride, max_sel, sel=None, wire_len=None, crc_out=None, fast=False):
     """Returns (wire, sel, wire_len, crc_out, sent_ms, (emitted, due)) after the call; `sel`,
     `wire_len`, `crc_out`: the prior contents of the optional outputs, None for a NULL pointer
-    (None comes back).  sel[k] is the global slot f * window + s."""
+    (None comes back).  sel[k] is the global slot f * window + s.  fast: the same with one
+    selection over all global slots and a loop over the emitted datagrams only, for states of
+    2^20 slots and rings of 10^5 entries (tests/test_txflows_model.py holds it to the per-flow
+    path, which is the definition)."""
     wire = np.array(wire, dtype=np.uint8, copy=True)
     sent = np.array(sent_ms, dtype=np.uint32, copy=True)
     outs = [None if a is None else np.array(a, dtype=np.uint32, copy=True) for a in (sel, wire_len, crc_out)]
+    if fast:
+        return _retransmit_var_flows_fast(base, base_bytes, offsets, lengths, nrec, seq0, rec0, rec_end, nflows, window, acked,
+                                          sent, now_ms, timeout_ms, flags, wire, wire_stride, max_sel, outs)
     emitted = due = 0
     for f in range(nflows):
         lo, inf = f * window, inflight_of(rec0, rec_end, f, window)
@@ -99,6 +145,53 @@ def retransmit_var_flows(base, base_bytes, offsets, lengths, nrec, seq0, rec0, r
                 a[k0:k0 + e] = v[:e]
         emitted, due = emitted + e, due + d
     return (wire, *outs, sent, (emitted, due))
+
+
+def _retransmit_var_flows_fast(base, base_bytes, offsets, lengths, nrec, seq0, rec0, rec_end, nflows, window, acked, sent,
+                               now_ms, timeout_ms, flags, wire, wire_stride, max_sel, outs):
+    """`wire`, `sent` and `outs` are the copies the caller made, written in place.  CRCs from
+    oracle.batch_var, the header words laid out as oracle.build_datagram lays them out."""
+    S = nflows * window
+    base = np.asarray(base, dtype=np.uint8)
+    g = np.arange(S, dtype=np.int64)
+    infl = inflight_all(rec0, rec_end, nflows, window)
+    age = (now_ms - sent[:S].astype(np.int64)) & M32
+    is_due = ((g % max(window, 1)) < np.repeat(infl, window)) & (np.asarray(acked)[:S] == 0) & \
+        (bool(flags & RETX_ALL) | (age > timeout_ms))
+    picked = np.flatnonzero(is_due)
+    due, picked = int(picked.size), picked[:max_sel]
+    e = int(picked.size)
+    sent[picked] = now_ms & M32
+    f, s = picked // max(window, 1), picked % max(window, 1)
+    rec = (np.asarray(rec0, dtype=np.int64)[f] + s) & M32
+    seq = (np.asarray(seq0, dtype=np.int64)[f] + s) & M32
+    there = rec < nrec
+    at = np.where(there, rec, 0)
+    tab_o, tab_l = np.asarray(offsets, dtype=np.uint64), np.asarray(lengths, dtype=np.uint32)
+    if nrec == 0:  # no record is looked up
+        tab_o, tab_l = np.zeros(1, np.uint64), np.zeros(1, np.uint32)
+    offs = np.where(there, tab_o[at], 0).astype(np.uint64)
+    lens = np.where(there, tab_l[at], INVALID_LEN).astype(np.int64)
+    valid = (lens <= MAXP) & (offs <= np.uint64(base_bytes))
+    valid[valid] = lens[valid] <= base_bytes - offs[valid].astype(np.int64)
+    v = np.flatnonzero(valid)
+    crc, wl = np.zeros(e, np.uint32), np.zeros(e, np.uint32)
+    crc[v] = O.batch_var(base, offs[v], lens[v].astype(np.uint32))
+    wl[v] = 16 + lens[v]
+    head = np.stack([np.full(v.size, 2), seq[v], lens[v], crc[v]], axis=1).astype(">u4").view(np.uint8).reshape(v.size, 16)
+    assert wire.size >= e * wire_stride
+    slots = wire[:e * wire_stride].reshape(e, wire_stride)
+    slots[v, :16] = head
+    src = offs[v].astype(np.int64)
+    for n in np.unique(lens[v]).tolist():  # the payloads, one length at a time, 4096 datagrams at a time
+        same = np.flatnonzero(lens[v] == n)
+        for a in range(0, same.size if n else 0, 4096):
+            part = same[a:a + 4096]
+            slots[v[part], 16:16 + n] = base[src[part][:, None] + np.arange(n)]
+    for a, x in zip(outs, (picked, wl, crc)):
+        if a is not None:
+            a[:e] = x
+    return (wire, *outs, sent, (e, due))
 
 
 # ---- the corpus of the randomised differential test -------------------------------------------
