@@ -18,36 +18,14 @@ Prints one JSON line and writes it to profiles/accept/accept_bench.json (--out).
 Goal (in-order, 1 M): accept_ms / (verify_ms + copy_ms) <= 1.10.
   python tools/accept_bench.py [--reps 25] [--warmup 3] [--sizes 1048576,65536]
                                [--orders inorder,permuted] [--out PATH]"""
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "a3-reliable-transport_amd"))
-import wtp_crc32 as W  # noqa: E402
+import bench_support as B  # first: it puts the binding's directory on sys.path
+import wtp_crc32 as W
+from bench_support import stats
 
 STRIDE, MAXP, SEQ0, GOAL = 1472, 1456, 1, 1.10
-
-
-def timed(fn, before=None):
-    if before:
-        before()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
 
 
 def case(n, order, reps, warmup):
@@ -96,49 +74,30 @@ def case(n, order, reps, warmup):
         exact = exact and bool(torch.equal(out, src) and bool(ok.all()))
     if not exact:
         raise SystemExit(f"accept_bench: n={n} {order}: outputs are not exact")
-    t = {"verify": [], "copy": [], "accept": []}
-    for rep in range(warmup + reps):
-        tv, tc, ta = timed(verify), timed(copy), timed(accept, before=reset)
-        if rep >= warmup:
-            t["verify"].append(tv)
-            t["copy"].append(tc)
-            t["accept"].append(ta)
+    t = B.sample({"verify": (verify, None, 1), "copy": (copy, None, 1), "accept": (accept, reset, 1)}, reps, warmup)
     base = np.asarray(t["verify"]) + np.asarray(t["copy"])
     v, c, a = (float(np.median(t[k])) for k in ("verify", "copy", "accept"))
     payload = float(total)
     return {"n": n, "order": order, "stride": STRIDE, "window": n, "exact": exact, "kernel": kernel,
             "verify_ms": round(v, 4), "copy_ms": round(c, 4), "accept_ms": round(a, 4),
             "ratio": round(a / (v + c), 4),
-            "baseline_ms": stats(base), "accept_ms_stats": stats(t["accept"]),
-            "baseline_spread": round(float((np.percentile(base, 75) - np.percentile(base, 25)) / np.median(base)), 4),
+            "baseline_ms": stats(base), "accept_ms_stats": stats(t["accept"]), "baseline_spread": B.spread(base),
             "accept_payload_gbps": round(payload / (a * 1e-3) / 1e9, 1),
             "place_ms_estimate": round(a - v, 4)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--sizes", default="1048576,65536")
     ap.add_argument("--orders", default="inorder,permuted")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "accept", "accept_bench.json"))
+    B.add_out(ap, "accept")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("accept_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 20:
-        raise SystemExit("accept_bench: --reps must be at least 20")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
+    res = B.start("accept_bench", a, min_reps=20)
     cases = [case(int(n), order, a.reps, a.warmup) for n in a.sizes.split(",") for order in a.orders.split(",")]
     head = next((c for c in cases if c["n"] == 1 << 20 and c["order"] == "inorder"), None)
-    res = {"tool": "accept_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup, "goal_ratio": GOAL,
-           "headline_ratio": head["ratio"] if head else None,
-           "goal_met": bool(head["ratio"] <= GOAL) if head else None, "cases": cases}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    res.update({"goal_ratio": GOAL, "headline_ratio": head["ratio"] if head else None,
+                "goal_met": bool(head["ratio"] <= GOAL) if head else None, "cases": cases})
+    B.write_result(res, a.out)
 
 
 if __name__ == "__main__":

@@ -15,43 +15,16 @@ vectorised path): counts, d_src and every ACK byte.  Goal: accep
 
 Prints one JSON line and writes it to profiles/ack/ack_bench.json (--out).
   python tools/ack_bench.py [--reps 25] [--warmup 3] [--sizes 1048576,65536] [--out PATH]"""
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for d in ("a3-reliable-transport_amd", "oracle", "tests"):
-    sys.path.insert(0, os.path.join(ROOT, d))
-import ack_model as A  # noqa: E402
-import wtp_crc32 as W  # noqa: E402
+import bench_support as B  # first: it puts the binding's and the model's directories on sys.path
+import ack_model as A
+import wtp_crc32 as W
+from bench_support import stats, u32
 
 STRIDE, MAXP, SEQ0 = 1472, 1456, 0xFFF80000
 MODES = (("selective", W.ACK_SELECTIVE), ("cumulative", W.ACK_CUMULATIVE))
-
-
-def timed(fn, before=None):
-    if before:
-        before()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 def case(n, permuted, reps, warmup):
@@ -96,12 +69,7 @@ def case(n, permuted, reps, warmup):
                      and int(seq[-1]) == (int(u32(ack)[0]) if mode == W.ACK_CUMULATIVE else int(seq[-1])))
         if not exact:
             raise SystemExit(f"ack_bench: n {n} {row['order']} {name}: outputs are not exact")
-        ta, tk = [], []
-        for rep in range(warmup + reps):
-            a, k = timed(accept, before=clear), timed(acks)
-            if rep >= warmup:
-                ta.append(a)
-                tk.append(k)
+        ta, tk = B.sample({"accept": (accept, clear, 1), "acks": (acks, None, 1)}, reps, warmup).values()
         ma, mk = float(np.median(ta)), float(np.median(tk))
         sa = stats(ta)
         row[name] = {"exact": exact, "kernel": W.LIB.wtp_last_kernel().decode(), "accept_ms": round(ma, 4),
@@ -113,27 +81,16 @@ def case(n, permuted, reps, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--sizes", default="1048576,65536")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ack", "ack_bench.json"))
+    B.add_out(ap, "ack")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("ack_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 20:
-        raise SystemExit("ack_bench: --reps must be at least 20")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
+    res = B.start("ack_bench", a, min_reps=20)
     rows = [case(int(n), permuted, a.reps, a.warmup) for n in a.sizes.split(",") for permuted in (False, True)]
     big = [r for r in rows if r["n"] == 1 << 20 and r["order"] == "in order"]
-    res = {"tool": "ack_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup, "goal_ratio": 1.10,
-           "goal_met": all(r[m]["ratio"] <= 1.10 for r in big for m, _ in MODES) if big else None, "cases": rows}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    res.update({"goal_ratio": 1.10, "goal_met": all(r[m]["ratio"] <= 1.10 for r in big for m, _ in MODES) if big else None,
+                "cases": rows})
+    B.write_result(res, a.out)
 
 
 if __name__ == "__main__":

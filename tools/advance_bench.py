@@ -22,44 +22,19 @@ by definition (the state; the image over each slot's stored length).
 Prints one JSON line and writes it to profiles/advance/advance_bench.json (--out).
 Acceptance: a < b at S1 and S2 by more than the sum of both interquartile ranges.
   python tools/advance_bench.py [--reps 25] [--warmup 3] [--configs S1,S2,Z,D] [--out PATH]"""
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "a3-reliable-transport_amd"))
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import oracle as O  # noqa: E402
-import wtp_crc32 as W  # noqa: E402
+import bench_support as B  # first: it puts the binding's and the oracle's directories on sys.path
+import oracle as O
+import wtp_crc32 as W
+from bench_support import iqr, stats
 
 STRIDE, MAXP, EMPTY, SEQ0 = 1472, 1456, 0xFFFFFFFF, 0xFFFFF000
 CONFIGS = {"S1": (1 << 20, 300000, "sparse"), "S2": (1 << 16, 20000, "sparse"), "Z": (1 << 20, 1, "zipf"),
            "D": (1 << 20, 1, "full")}
 GATED = ("S1", "S2")
 NEXT_BATCH = 65536  # datagrams of the next round's accept in route (v)
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
-
-
-def iqr(xs):
-    return float(np.percentile(xs, 75) - np.percentile(xs, 25))
 
 
 def lengths(w, a, kind):
@@ -155,12 +130,7 @@ def case(name, reps, warmup):
     exact = exact and torch.equal(c_dst, c_src) and bool((ok == 1).all())
     if not exact:
         raise SystemExit(f"advance_bench: {name}: outputs are not exact")
-    t = {"a": [], "b": [], "r": [], "c": [], "v": []}
-    for rep in range(warmup + reps):
-        ts = (timed(a_new), timed(b_torch), timed(b_read), timed(c_copy), timed(v_next))
-        if rep >= warmup:
-            for k, x in zip("abrcv", ts):
-                t[k].append(x)
+    t = B.sample({k: (fn, None, 1) for k, fn in zip("abrcv", (a_new, b_torch, b_read, c_copy, v_next))}, reps, warmup)
     ma, mb, mr, mc, mv = (float(np.median(t[k])) for k in "abrcv")
     traffic = 8 * w + 2 * moved  # per slot 4 B read + 4 B written, + 2 v for a valid slot
     return {"config": name, "window": w, "advance": a, "contents": kind, "filled_slots_moved": int((v <= MAXP).sum()),
@@ -169,32 +139,20 @@ def case(name, reps, warmup):
             "v_advance_then_accept_ms": round(mv, 4), "a_over_b": round(ma / mb, 4), "a_over_c": round(ma / mc, 4),
             "a_stats": stats(t["a"]), "b_stats": stats(t["b"]), "b_read_stats": stats(t["r"]), "c_stats": stats(t["c"]),
             "v_stats": stats(t["v"]), "a_iqr_ms": round(iqr(t["a"]), 4), "b_iqr_ms": round(iqr(t["b"]), 4),
-            "a_below_b_by_more_than_both_iqr": bool(mb - ma > iqr(t["a"]) + iqr(t["b"])), "gated": name in GATED,
+            "a_below_b_by_more_than_both_iqr": B.below_by_more_than_both_iqr(t["a"], t["b"]), "gated": name in GATED,
             "b_bytes_copied": (w - a) * (MAXP + 4) + 4 * a, "a_model_traffic_bytes": traffic,
             "a_model_traffic_gbps": round(traffic / (ma * 1e-3) / 1e9, 1)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--configs", default="S1,S2,Z,D")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "advance", "advance_bench.json"))
+    B.add_out(ap, "advance")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("advance_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 20:
-        raise SystemExit("advance_bench: --reps must be at least 20")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()  # route (v)'s accept
+    res = B.start("advance_bench", a, min_reps=20)
     cases = [case(c, a.reps, a.warmup) for c in a.configs.split(",")]
-    res = {"tool": "advance_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup,
-           "accepted": all(c["a_below_b_by_more_than_both_iqr"] for c in cases if c["gated"]), "cases": cases}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    res.update({"accepted": all(c["a_below_b_by_more_than_both_iqr"] for c in cases if c["gated"]), "cases": cases})
+    B.write_result(res, a.out)
 
 
 if __name__ == "__main__":

@@ -16,35 +16,18 @@ Also reported: the buffer call at 64 KiB (the C2 size) and, at both sizes, from 
 Prints one JSON line and writes it to profiles/buffer/buffer_bench.json (--out).
 Goal (1 M chunks, aligned): buffer_ms / batch_fixed_ms <= 1.10.
   python tools/buffer_bench.py [--reps 25] [--warmup 3] [--chunks 1048576] [--out PATH]"""
-import argparse
 import hashlib
 import json
 import os
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "a3-reliable-transport_amd"))
-import wtp_crc32 as W  # noqa: E402
+import bench_support as B  # first: it puts the binding's directory on sys.path
+import wtp_crc32 as W
+from bench_support import stats
 
 MAXP, GOAL, OFF = 1456, 1.10, 8
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
 
 
 def host_fold(crcs, last_len):
@@ -55,7 +38,7 @@ def host_fold(crcs, last_len):
 
 
 def u32(t):
-    return int(t.cpu().numpy().view(np.uint32)[0])
+    return int(B.u32(t)[0])
 
 
 def headline(n, reps, warmup):
@@ -84,7 +67,7 @@ def headline(n, reps, warmup):
     vec = crcs.cpu().numpy().view(np.uint32)
     want = host_fold(vec, MAXP)
     sha = hashlib.sha256(vec.astype("<u4").tobytes()).hexdigest()
-    with open(os.path.join(ROOT, "tests", "golden", "bench_digests.json")) as f:
+    with open(os.path.join(B.ROOT, "tests", "golden", "bench_digests.json")) as f:
         ref_sha = json.load(f)["sha256_by_packets"].get(str(n))
     whole()
     got_buffer = u32(out)
@@ -108,14 +91,8 @@ def headline(n, reps, warmup):
     def whole_off():
         W.crc32_buffer(mis, total - OFF, out, work=bwork)
 
-    t = {"fixed": [], "buffer": [], "concat": [], "buffer_off8": []}
-    for rep in range(warmup + reps):
-        ta, tb, tc, to = timed(fixed), timed(whole), timed(concat), timed(whole_off)
-        if rep >= warmup:
-            t["fixed"].append(ta)
-            t["buffer"].append(tb)
-            t["concat"].append(tc)
-            t["buffer_off8"].append(to)
+    t = B.sample({"fixed": (fixed, None, 1), "buffer": (whole, None, 1), "concat": (concat, None, 1),
+                  "buffer_off8": (whole_off, None, 1)}, reps, warmup)
     a, b, c, o = (float(np.median(t[k])) for k in ("fixed", "buffer", "concat", "buffer_off8"))
     return {"chunks": n, "bytes": total, "check": check, "offset8_check": bool(offset_ok),
             "kernels": [fixed_kernel, fold_kernel],
@@ -123,7 +100,7 @@ def headline(n, reps, warmup):
             "buffer_off8_ms": round(o, 4), "ratio": round(b / a, 4), "ratio_off8": round(o / a, 4),
             "batch_fixed_stats": stats(t["fixed"]), "buffer_stats": stats(t["buffer"]),
             "concat_stats": stats(t["concat"]), "buffer_off8_stats": stats(t["buffer_off8"]),
-            "batch_fixed_spread": round(float((np.percentile(t["fixed"], 75) - np.percentile(t["fixed"], 25)) / a), 4),
+            "batch_fixed_spread": B.spread(t["fixed"]),
             "buffer_gbps": round(total / (b * 1e-3) / 1e9, 1)}
 
 
@@ -144,34 +121,22 @@ def small(nbytes, reps, warmup):
         call()
         if u32(out) != W.crc32(host[off:off + nbytes].tobytes()):
             raise SystemExit(f"buffer_bench: {nbytes} B at offset {off}: wrong CRC")
-        ts = [timed(call) for _ in range(warmup + reps)][warmup:]
+        ts = B.sample({name: (call, None, 1)}, reps, warmup)[name]
         res[name + "_ms"] = round(float(np.median(ts)), 4)
         res[name + "_stats"] = stats(ts)
     return res
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--chunks", type=int, default=1 << 20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "buffer", "buffer_bench.json"))
+    B.add_out(ap, "buffer")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("buffer_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 25:
-        raise SystemExit("buffer_bench: --reps must be at least 25")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
+    res = B.start("buffer_bench", a, min_reps=25)
     head = headline(a.chunks, a.reps, a.warmup)
-    res = {"tool": "buffer_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup, "goal_ratio": GOAL,
-           "headline_ratio": head["ratio"], "goal_met": bool(head["ratio"] <= GOAL), "headline": head,
-           "c2_64KiB": small(65536, a.reps, a.warmup)}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    res.update({"goal_ratio": GOAL, "headline_ratio": head["ratio"], "goal_met": bool(head["ratio"] <= GOAL), "headline": head,
+                "c2_64KiB": small(65536, a.reps, a.warmup)})
+    B.write_result(res, a.out)
 
 
 if __name__ == "__main__":

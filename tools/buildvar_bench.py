@@ -17,41 +17,16 @@ every slot against the source, and for the 1456-B batch the whole ring against (
 Prints one JSON line and writes it to profiles/buildvar/buildvar_bench.json (--out).
 Goal (1 M Zipf): a / (b + c) <= 1.10, both sides from the same run.
   python tools/buildvar_bench.py [--reps 25] [--warmup 3] [--batches zipf_1m,zipf_64k,full_1m] [--out PATH]"""
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "a3-reliable-transport_amd"))
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import oracle as O  # noqa: E402
-import wtp_crc32 as W  # noqa: E402
+import bench_support as B  # first: it puts the binding's and the oracle's directories on sys.path
+import oracle as O
+import wtp_crc32 as W
+from bench_support import stats
 
 STRIDE, MAXP, SEQ0, GOAL = 1472, 1456, 0xFFFFF000, 1.10
 BATCHES = {"zipf_1m": (1 << 20, "zipf"), "zipf_64k": (1 << 16, "zipf"), "full_1m": (1 << 20, "full")}
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
-
-
-def spread(xs):
-    return round(float((np.percentile(xs, 75) - np.percentile(xs, 25)) / np.median(xs)), 4)
 
 
 def check_exact(n, lens, offs, host, src, wire, wl, crc):
@@ -120,12 +95,7 @@ def case(name, reps, warmup):
         del ring_a
     if not exact:
         raise SystemExit(f"buildvar_bench: {name}: outputs are not exact")
-    t = {"a": [], "b": [], "c": [], "d": []}
-    for rep in range(warmup + reps):
-        ts = (timed(a_new), timed(b_crc), timed(c_copy), timed(d_fixed))
-        if rep >= warmup:
-            for k, v in zip("abcd", ts):
-                t[k].append(v)
+    t = B.sample({k: (fn, None, 1) for k, fn in zip("abcd", (a_new, b_crc, c_copy, d_fixed))}, reps, warmup)
     two_pass = np.asarray(t["b"]) + np.asarray(t["c"])
     a, b, c, d = (float(np.median(t[k])) for k in "abcd")
     traffic = 2 * total + 12 * n + 16 * n + 8 * n  # reads len + 12 B, writes 16 + len + 8 B per datagram
@@ -135,33 +105,21 @@ def case(name, reps, warmup):
             "d_build_fixed_ms": round(d, 4), "d_chunks": n_d,
             "a_over_b_plus_c": round(a / (b + c), 4), "a_over_d": round(a / d, 4),
             "a_stats": stats(t["a"]), "b_plus_c_stats": stats(two_pass), "d_stats": stats(t["d"]),
-            "a_spread": spread(t["a"]), "b_plus_c_spread": spread(two_pass),
+            "a_spread": B.spread(t["a"]), "b_plus_c_spread": B.spread(two_pass),
             "a_model_traffic_gbps": round(traffic / (a * 1e-3) / 1e9, 1)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--batches", default="zipf_1m,zipf_64k,full_1m")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "buildvar", "buildvar_bench.json"))
+    B.add_out(ap, "buildvar")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("buildvar_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 20:
-        raise SystemExit("buildvar_bench: --reps must be at least 20")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
+    res = B.start("buildvar_bench", a, min_reps=20)
     cases = [case(b, a.reps, a.warmup) for b in a.batches.split(",")]
     head = next((c for c in cases if c["batch"] == "zipf_1m"), None)
-    res = {"tool": "buildvar_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup, "goal_ratio": GOAL,
-           "headline_ratio": head["a_over_b_plus_c"] if head else None,
-           "goal_met": bool(head["a_over_b_plus_c"] <= GOAL) if head else None, "cases": cases}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    res.update({"goal_ratio": GOAL, "headline_ratio": head["a_over_b_plus_c"] if head else None,
+                "goal_met": bool(head["a_over_b_plus_c"] <= GOAL) if head else None, "cases": cases})
+    B.write_result(res, a.out)
 
 
 if __name__ == "__main__":

@@ -18,41 +18,16 @@ source, d_offsets_out / d_lengths_out / d_counts against the lengths, (b) agains
 Prints one JSON line and writes it to profiles/deliver/deliver_bench.json (--out).
 Acceptance: a < b at every window by more than the sum of both interquartile ranges.
   python tools/deliver_bench.py [--reps 25] [--warmup 3] [--batches zipf_1m,zipf_64k,full_1m] [--out PATH]"""
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "a3-reliable-transport_amd"))
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import oracle as O  # noqa: E402
-import wtp_crc32 as W  # noqa: E402
+import bench_support as B  # first: it puts the binding's and the oracle's directories on sys.path
+import oracle as O
+import wtp_crc32 as W
+from bench_support import iqr, stats
 
 STRIDE, MAXP, SEQ0 = 1472, 1456, 0xFFFFF000
 BATCHES = {"zipf_1m": (1 << 20, "zipf"), "zipf_64k": (1 << 16, "zipf"), "full_1m": (1 << 20, "full")}
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
-
-
-def iqr(xs):
-    return float(np.percentile(xs, 75) - np.percentile(xs, 25))
 
 
 def case(name, reps, warmup):
@@ -112,12 +87,7 @@ def case(name, reps, warmup):
     exact = exact and torch.equal(got_b[0], src) and torch.equal(dst, src) and bool((ok_v == 1).all())
     if not exact:
         raise SystemExit(f"deliver_bench: {name}: outputs are not exact")
-    t = {"a": [], "b": [], "c": [], "v": []}
-    for rep in range(warmup + reps):
-        ts = (timed(a_new), timed(b_torch), timed(c_copy), timed(v_next))
-        if rep >= warmup:
-            for k, x in zip("abcv", ts):
-                t[k].append(x)
+    t = B.sample({k: (fn, None, 1) for k, fn in zip("abcv", (a_new, b_torch, c_copy, v_next))}, reps, warmup)
     a, b, c, v = (float(np.median(t[k])) for k in "abcv")
     traffic = (total + 4 * n) + (total + 12 * n)  # reads len + 4 B, writes len + 12 B per record
     return {"batch": name, "n": n, "delivered_bytes": total, "mean_len": round(total / n, 1), "exact": exact,
@@ -125,32 +95,20 @@ def case(name, reps, warmup):
             "v_deliver_then_verify_ms": round(v, 4), "a_over_b": round(a / b, 4), "a_over_c": round(a / c, 4),
             "a_stats": stats(t["a"]), "b_stats": stats(t["b"]), "c_stats": stats(t["c"]), "v_stats": stats(t["v"]),
             "a_iqr_ms": round(iqr(t["a"]), 4), "b_iqr_ms": round(iqr(t["b"]), 4),
-            "a_below_b_by_more_than_both_iqr": bool(b - a > iqr(t["a"]) + iqr(t["b"])),
+            "a_below_b_by_more_than_both_iqr": B.below_by_more_than_both_iqr(t["a"], t["b"]),
             "a_model_traffic_gbps": round(traffic / (a * 1e-3) / 1e9, 1),
             "a_payload_read_plus_write_gbps": round(2 * total / (a * 1e-3) / 1e9, 1)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--batches", default="zipf_1m,zipf_64k,full_1m")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deliver", "deliver_bench.json"))
+    B.add_out(ap, "deliver")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("deliver_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 20:
-        raise SystemExit("deliver_bench: --reps must be at least 20")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
+    res = B.start("deliver_bench", a, min_reps=20)
     cases = [case(b, a.reps, a.warmup) for b in a.batches.split(",")]
-    res = {"tool": "deliver_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup,
-           "accepted": all(c["a_below_b_by_more_than_both_iqr"] for c in cases), "cases": cases}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    res.update({"accepted": all(c["a_below_b_by_more_than_both_iqr"] for c in cases), "cases": cases})
+    B.write_result(res, a.out)
 
 
 if __name__ == "__main__":

@@ -22,36 +22,18 @@ d_place is the slot within the flow, the per-flow ACKs are seq0[f] + window.
 
 Prints one JSON line and writes it to profiles/flows/flows_bench.json (--out).
   python tools/flows_bench.py [--reps 25] [--warmup 3] [--inner 50] [--flows 1,64,1024,16384] [--out PATH]"""
-import argparse
-import json
-import os
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for d in ("a3-reliable-transport_amd", "oracle", "tests"):
-    sys.path.insert(0, os.path.join(ROOT, d))
-import wtp_crc32 as W  # noqa: E402
+import bench_support as B  # first: it puts the binding's directory on sys.path
+import wtp_crc32 as W
+from bench_support import stats, u32, z
 
 N, STRIDE, MAXP, SEQ0 = 1 << 16, 1472, 1456, 0xFFFF8000  # the one-connection window wraps 2^32
 MODES = (("selective", W.ACK_SELECTIVE), ("cumulative", W.ACK_CUMULATIVE))
 SPLIT_MAX_FLOWS = 1024
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs, dtype=np.float64))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def z(k, dtype=torch.int32):
-    return torch.zeros(k, dtype=dtype, device="cuda")
 
 
 class State:
@@ -64,27 +46,6 @@ class State:
 
     def clear(self):
         self.sl.fill_(-1)
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def graph_of(fn):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    s.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        fn()
-    return g
 
 
 def case(nflows, mode_name, mode, ordered, reps, warmup, inner):
@@ -152,21 +113,10 @@ def case(nflows, mode_name, mode, ordered, reps, warmup, inner):
 
     # ---- timing ------------------------------------------------------------------------------------
     row = {"nflows": nflows, "window": window, "mode": mode_name, "exact": exact, "n": N}
+    # a unit of the split baseline is already nflows call pairs
+    calls = {name: (fn, max(1, inner // nflows) if name == "b" else inner) for name, fn in variants.items()}
     for how in ("graph", "back_to_back"):
-        units = {}
-        for name, fn in variants.items():
-            # a unit of the split baseline is already nflows call pairs
-            k = max(1, inner // nflows) if name == "b" else inner
-            many = (lambda fn=fn, k=k: [fn() for _ in range(k)])
-            units[name] = (graph_of(many).replay if how == "graph" else many, k)
-        names = sorted(units)
-        t = {name: [] for name in names}
-        for rep in range(warmup + reps):
-            for name in (names if rep % 2 == 0 else names[::-1]):
-                run, k = units[name]
-                ms = timed(run) / k
-                if rep >= warmup:
-                    t[name].append(ms)
+        t = B.sample(B.repeated(calls, how), reps, warmup, alternate=True)
         med = {name: float(np.median(v)) for name, v in t.items()}
         res = {"unit_ms": {name: stats(v) for name, v in t.items()},
                "flows_over_a": round(med["flows"] / med["a"], 4),
@@ -181,19 +131,13 @@ def case(nflows, mode_name, mode, ordered, reps, warmup, inner):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--inner", type=int, default=50)
     ap.add_argument("--flows", default="1,64,1024,16384")
     ap.add_argument("--modes", default="selective,cumulative")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "flows", "flows_bench.json"))
+    B.add_out(ap, "flows")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("flows_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 10:
-        raise SystemExit("flows_bench: --reps must be at least 10")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
+    res = B.start("flows_bench", a, min_reps=10)
     pay = torch.empty(N * MAXP, dtype=torch.uint8, device="cuda")
     W.synth_fill(pay, seed=0xF10)
     ring0 = torch.empty((N, STRIDE), dtype=torch.uint8, device="cuda")
@@ -206,14 +150,9 @@ def main():
             if name in a.modes.split(","):
                 rows.append(case(int(f), name, mode, (ring0, rl), a.reps, a.warmup, a.inner))
                 print(f"flows_bench: nflows {f} {name} done", file=sys.stderr, flush=True)
-    res = {"tool": "flows_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup, "inner": a.inner,
-           "unit": "clear d_slot_len; accept; acks over the whole batch (b: nflows call pairs); ms per unit", "cases": rows}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    res.update({"inner": a.inner, "unit": "clear d_slot_len; accept; acks over the whole batch (b: nflows call pairs); ms per unit",
+                "cases": rows})
+    B.write_result(res, a.out)
 
 
 if __name__ == "__main__":

@@ -25,53 +25,18 @@ moved by that, and at F == 1 everything equals (c) too.
 Prints one JSON line and writes it to profiles/flows_flush/flows_flush_bench.json (--out).
   python tools/flows_flush_bench.py [--reps 25] [--warmup 3] [--inner 20] [--flows 1,64,1024,16384]
                                     [--lengths full,zipf] [--out PATH]"""
-import argparse
-import json
-import os
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for d in ("a3-reliable-transport_amd", "oracle", "tests"):
-    sys.path.insert(0, os.path.join(ROOT, d))
-import oracle as O  # noqa: E402
-import wtp_crc32 as W  # noqa: E402
+import bench_support as B  # first: it puts the binding's and the oracle's directories on sys.path
+import oracle as O
+import wtp_crc32 as W
+from bench_support import stats, z
 
 N, STRIDE, MAXP, SEQ0 = 1 << 16, 1472, 1456, 0xFFFF8000
 SPLIT_MAX_FLOWS = 1024
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs, dtype=np.float64))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
-
-
-def z(k, dtype=torch.int32, fill=0):
-    return torch.full((k,), fill, dtype=dtype, device="cuda")
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def graph_of(fn):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    s.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        fn()
-    return g
 
 
 class Out:
@@ -157,20 +122,10 @@ def case(nflows, kind, lens_h, wire, reps, warmup, inner):
 
     # ---- timing ------------------------------------------------------------------------------------
     row = {"nflows": nflows, "window": window, "lengths": kind, "exact": exact, "slots": N, "delivered_bytes": total}
+    # a unit of the split baseline is already nflows call pairs
+    calls = {name: (fn, max(1, inner // nflows) if name == "b" else inner) for name, fn in variants.items()}
     for how in ("graph", "back_to_back"):
-        units = {}
-        for name, fn in variants.items():
-            k = max(1, inner // nflows) if name == "b" else inner  # a unit of the split baseline is already nflows call pairs
-            many = (lambda fn=fn, k=k: [fn() for _ in range(k)])
-            units[name] = (graph_of(many).replay if how == "graph" else many, k)
-        names = sorted(units)
-        t = {name: [] for name in names}
-        for rep in range(warmup + reps):
-            for name in (names if rep % 2 == 0 else names[::-1]):
-                run, k = units[name]
-                ms = timed(run) / k
-                if rep >= warmup:
-                    t[name].append(ms)
+        t = B.sample(B.repeated(calls, how), reps, warmup, alternate=True)
         med = {name: float(np.median(v)) for name, v in t.items()}
         res = {"unit_ms": {name: stats(v) for name, v in t.items()},
                "a_over_c": round(med["a"] / med["c"], 4),
@@ -178,28 +133,20 @@ def case(nflows, kind, lens_h, wire, reps, warmup, inner):
                "a_over_c_paired": stats(np.divide(t["a"], t["c"])),
                "c2_over_c_paired": stats(np.divide(t["c2"], t["c"]))}
         if split:
-            sa, sb = res["unit_ms"]["a"], res["unit_ms"]["b"]
             res["b_over_a"] = round(med["b"] / med["a"], 2)
-            # the ordering gate: (a) below (b) by more than both interquartile ranges
-            res["a_below_b_by_more_than_both_iqr"] = bool(sb["median"] - sa["median"] > (sa["p75"] - sa["p25"]) + (sb["p75"] - sb["p25"]))
+            res["a_below_b_by_more_than_both_iqr"] = B.below_by_more_than_both_iqr(t["a"], t["b"])
         row[how] = res
     return row
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--flows", default="1,64,1024,16384")
     ap.add_argument("--lengths", default="full,zipf")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "flows_flush", "flows_flush_bench.json"))
+    B.add_out(ap, "flows_flush")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("flows_flush_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 10:
-        raise SystemExit("flows_flush_bench: --reps must be at least 10")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
+    res = B.start("flows_flush_bench", a, min_reps=10)
     rows = []
     for kind in a.lengths.split(","):
         lens_h = np.full(N, MAXP, np.uint32) if kind == "full" else O.zipf_lengths(N, seed=0xF1A).astype(np.uint32)
@@ -216,15 +163,10 @@ def main():
         for f in a.flows.split(","):
             rows.append(case(int(f), kind, lens_h, (ring0, rl0), a.reps, a.warmup, a.inner))
             print(f"flows_flush_bench: nflows {f} {kind} done", file=sys.stderr, flush=True)
-    res = {"tool": "flows_flush_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup, "inner": a.inner,
-           "unit": "deliver (max_slots = window / 2) + advance over the whole state (b: nflows call pairs); ms per unit",
-           "cases": rows}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    res.update({"inner": a.inner,
+                "unit": "deliver (max_slots = window / 2) + advance over the whole state (b: nflows call pairs); ms per unit",
+                "cases": rows})
+    B.write_result(res, a.out)
 
 
 if __name__ == "__main__":

@@ -21,40 +21,14 @@ equal the builder's wire image of the same buffer.  No target ratio is fixed.
 
 Prints one JSON line and writes it to profiles/retx/retx_bench.json (--out).
   python tools/retx_bench.py [--reps 25] [--warmup 3] [--inflight 65536] [--out PATH]"""
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "a3-reliable-transport_amd"))
-import wtp_crc32 as W  # noqa: E402
+import bench_support as B  # first: it puts the binding's directory on sys.path
+import wtp_crc32 as W
+from bench_support import i32, stats
 
 STRIDE, MAXP, SEQ0, NOW, TIMEOUT = 1472, 1456, 0xFFFF8000, 10_000, 500
-
-
-def timed(fn, before=None):
-    if before:
-        before()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
-
-
-def i32(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
 
 
 def ingest_case(inflight, reps, warmup):
@@ -80,12 +54,7 @@ def ingest_case(inflight, reps, warmup):
                  and torch.equal(hit, i32(perm)))
     if not exact:
         raise SystemExit("retx_bench: ingest outputs are not exact")
-    t, tv = [], []
-    for rep in range(warmup + reps):
-        a, v = timed(run, before=acked.zero_), timed(verify)
-        if rep >= warmup:
-            t.append(a)
-            tv.append(v)
+    t, tv = B.sample({"ingest": (run, acked.zero_, 1), "verify": (verify, None, 1)}, reps, warmup).values()
     return {"inflight": inflight, "n": inflight, "mode": "selective", "stride": 16, "exact": exact,
             "ingest_ms": round(float(np.median(t)), 4), "ingest_ms_stats": stats(t),
             "verify_batch_ms": round(float(np.median(tv)), 4), "acks_per_us": round(inflight / (np.median(t) * 1e3), 1)}
@@ -142,13 +111,7 @@ def retx_cases(inflight, reps, warmup):
                          and torch.equal(wire[:due - 1], image[idx][:due - 1]))
             if not exact:
                 raise SystemExit(f"retx_bench: fraction {frac} max_sel {max_sel}: outputs are not exact")
-            t = {"retx": [], "build": [], "crc": []}
-            for rep in range(warmup + reps):
-                tr, tb, tc = timed(retx, before=restore), timed(build), timed(crc_only)
-                if rep >= warmup:
-                    t["retx"].append(tr)
-                    t["build"].append(tb)
-                    t["crc"].append(tc)
+            t = B.sample({"retx": (retx, restore, 1), "build": (build, None, 1), "crc": (crc_only, None, 1)}, reps, warmup)
             r, b, c = (float(np.median(t[k])) for k in ("retx", "build", "crc"))
             row[label] = {"max_sel": max_sel, "exact": exact, "kernel": kernel,
                           "retx_ms": round(r, 4), "build_ms": round(b, 4), "ratio": round(r / b, 4),
@@ -160,25 +123,13 @@ def retx_cases(inflight, reps, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--inflight", type=int, default=65536)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "retx", "retx_bench.json"))
+    B.add_out(ap, "retx")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("retx_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 20:
-        raise SystemExit("retx_bench: --reps must be at least 20")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
-    res = {"tool": "retx_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup,
-           "ingest": ingest_case(a.inflight, a.reps, a.warmup), "retransmit": retx_cases(a.inflight, a.reps, a.warmup)}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    res = B.start("retx_bench", a, min_reps=20)
+    res.update({"ingest": ingest_case(a.inflight, a.reps, a.warmup), "retransmit": retx_cases(a.inflight, a.reps, a.warmup)})
+    B.write_result(res, a.out)
 
 
 if __name__ == "__main__":

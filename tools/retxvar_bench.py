@@ -27,9 +27,7 @@ Prints one JSON line and writes it to profiles/retxvar/retxvar_bench.json (--out
 --trace touches no device itself: it starts, one after the other, one child per configuration
 under `rocprofv3 --kernel-trace --stats` (ring = the window) and writes the per-kernel
 durations (tools/kstats.py's columns, split by grid) under one heading per configuration."""
-import argparse
 import glob
-import json
 import os
 import shutil
 import sqlite3
@@ -38,49 +36,20 @@ import sys
 import tempfile
 
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "a3-reliable-transport_amd"))
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import bench_support as B  # first: it puts the binding's and the oracle's directories on sys.path
+from bench_support import i32, iqr, stats
 
 STRIDE, MAXP, SEQ0, NOW, TIMEOUT = 1472, 1456, 0xFFFF8000, 10_000, 500
 SETS, FRACTIONS = ("full", "zipf"), (0.01, 0.1, 1.0)
 
 
-def stats(xs):
-    a = np.sort(np.asarray(xs))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
-
-
-def iqr(xs):
-    return float(np.percentile(xs, 75) - np.percentile(xs, 25))
-
-
 def bench(a):
-    import torch
-
-    import oracle as O
+    import oracle as O  # here, not at the top: --trace's parent loads no library
     import wtp_crc32 as W
 
-    def timed(fn, before=None):
-        if before:
-            before()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
-    def i32(x):
-        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint32).view(np.int32)).cuda()
-
-    if not torch.cuda.is_available():
-        raise SystemExit("retxvar_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 20 and not a.short:
-        raise SystemExit("retxvar_bench: --reps must be at least 20")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()  # wtp_crc32_batch_var, not the call under test
+    head = B.start("retxvar_bench", a, min_reps=0 if a.short else 20)
     inflight = a.inflight
     wanted = [c.split(":") for c in a.configs.split(",")] if a.configs else [(s, str(f)) for s in SETS for f in FRACTIONS]
     rows = []
@@ -154,14 +123,10 @@ def bench(a):
                     exact = exact and torch.equal(fwire[:due], wire[:due])
                 if not exact:
                     raise SystemExit(f"retxvar_bench: set {kind} fraction {frac} max_sel {max_sel}: outputs are not exact")
-                t = {"var": [], "build": [], "fixed": [], "3pass": []}
-                for rep in range(a.warmup + a.reps):
-                    ts = {"var": timed(var, before=restore), "build": timed(build), "3pass": timed(three_pass)}
-                    if kind == "full":
-                        ts["fixed"] = timed(fixed, before=restore)
-                    if rep >= a.warmup:
-                        for k, v in ts.items():
-                            t[k].append(v)
+                units = {"var": (var, restore, 1), "build": (build, None, 1), "3pass": (three_pass, None, 1)}
+                if kind == "full":
+                    units["fixed"] = (fixed, restore, 1)
+                t = B.sample(units, a.reps, a.warmup)
                 v, b, p = (float(np.median(t[k])) for k in ("var", "build", "3pass"))
                 res = {"max_sel": max_sel, "exact": exact, "kernel": kernel, "var_ms": round(v, 4), "build_var_ms": round(b, 4),
                        "var_over_build": round(v / b, 4), "three_pass_ms": round(p, 4), "var_over_three_pass": round(v / p, 4),
@@ -171,17 +136,11 @@ def bench(a):
                     f = float(np.median(t["fixed"]))
                     res.update({"fixed_ms": round(f, 4), "fixed_ms_stats": stats(t["fixed"]), "var_over_fixed": round(v / f, 4),
                                 "var_minus_fixed_ms": round(v - f, 4), "two_iqr_ms": round(iqr(t["var"]) + iqr(t["fixed"]), 4),
-                                "slower_than_fixed_beyond_two_iqr": bool(v - f > iqr(t["var"]) + iqr(t["fixed"]))})
+                                "slower_than_fixed_beyond_two_iqr": B.below_by_more_than_both_iqr(t["fixed"], t["var"])})
                 row[label] = res
             rows.append(row)
         del src, image, wire, ywire, fwire
-    res = {"tool": "retxvar_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup, "rows": rows}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    B.write_result({**head, "rows": rows}, a.out)
 
 
 def kernel_table(folder):
@@ -217,16 +176,14 @@ def trace(a):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--inflight", type=int, default=65536)
     ap.add_argument("--configs", default="", help="set:fraction,... (default: every set and fraction)")
     ap.add_argument("--ring", default="", help="ring_inflight or ring_due only")
     ap.add_argument("--short", action="store_true", help="allow fewer than 20 repetitions (not for committed figures)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "retxvar", "retxvar_bench.json"))
+    B.add_out(ap, "retxvar")
     ap.add_argument("--trace", action="store_true")
-    ap.add_argument("--trace-out", default=os.path.join(ROOT, "profiles", "retxvar", "kernel_trace.txt"))
+    ap.add_argument("--trace-out", default=os.path.join(B.ROOT, "profiles", "retxvar", "kernel_trace.txt"))
     a = ap.parse_args()
     trace(a) if a.trace else bench(a)
 

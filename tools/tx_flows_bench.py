@@ -29,41 +29,19 @@ selection and every emitted datagram against the reference ring.
 
 Prints one JSON line and writes it to profiles/tx_flows/tx_flows_bench.json (--out).
   python tools/tx_flows_bench.py [--reps 25] [--warmup 3] [--inner 10] [--flows 1,64,1024,16384] [--out PATH]"""
-import argparse
-import json
-import os
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for d in ("a3-reliable-transport_amd", "oracle", "tests"):
-    sys.path.insert(0, os.path.join(ROOT, d))
-import wtp_crc32 as W  # noqa: E402
+import bench_support as B  # first: it puts the binding's directory on sys.path
+import wtp_crc32 as W
+from bench_support import i32, stats, u32, z
 
 S, STRIDE, MAXP, SEQ0, NACK = 1 << 16, 1472, 1456, 0xFFFF8000, 4096  # the numbering wraps 2^32
 NOW, TIMEOUT = 100000, 500
 MODES = (("selective", W.ACK_SELECTIVE), ("cumulative", W.ACK_CUMULATIVE))
 SPLIT_MAX_FLOWS = 1024
-
-
-def stats(xs):
-    a = np.sort(np.asarray(xs, dtype=np.float64))
-    return {"median": round(float(np.median(a)), 4), "min": round(float(a[0]), 4), "max": round(float(a[-1]), 4),
-            "p25": round(float(np.percentile(a, 25)), 4), "p75": round(float(np.percentile(a, 75)), 4)}
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def z(k, dtype=torch.int32):
-    return torch.zeros(k, dtype=dtype, device="cuda")
 
 
 def ack_ring(seqs):
@@ -77,7 +55,7 @@ class State:
     """One variant's own window state and outputs (so that no variant warms another's)."""
 
     def __init__(self, nflows, sent0):
-        self.acked0, self.sent0 = z(S), dev(sent0)
+        self.acked0, self.sent0 = z(S), i32(sent0)
         self.acked, self.sent = [z(S), z(S)], [z(S), z(S)]
         self.ok, self.wire = z(NACK, torch.uint8), torch.empty((S, STRIDE), dtype=torch.uint8, device="cuda")
         self.sel, self.wl, self.counts = z(S), z(S), z(2)
@@ -86,27 +64,6 @@ class State:
     def restore(self):
         self.acked[0].copy_(self.acked0)
         self.sent[0].copy_(self.sent0)
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def graph_of(fn):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    s.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        fn()
-    return g
 
 
 def case(nflows, mode_name, mode, due, table, ref, reps, warmup, inner):
@@ -125,10 +82,10 @@ def case(nflows, mode_name, mode, due, table, ref, reps, warmup, inner):
     rec0_h = (np.arange(nflows) * window).astype(np.uint32)
     ring_f = ack_ring((seq0_h[a_flow].astype(np.int64) + a_slot + cum) & 0xFFFFFFFF)
     ring_a = ack_ring((SEQ0 + a_glob + cum) & 0xFFFFFFFF)
-    flow, rl = dev(a_flow), dev(np.full(NACK, 16))
-    rec_end = dev(rec0_h + window)
+    flow, rl = i32(a_flow), i32(np.full(NACK, 16))
+    rec_end = i32(rec0_h + window)
     fl, a1, a2 = State(nflows, sent0), State(1, sent0), State(1, sent0)
-    seq0, rec0 = dev(seq0_h), dev(rec0_h)
+    seq0, rec0 = i32(seq0_h), i32(rec0_h)
     bases = [[z(nflows), z(nflows)], [z(nflows), z(nflows)]]  # seq, rec: [current, next]
     work = torch.empty(W.tx_work_bytes(S, S), dtype=torch.uint8, device="cuda")
     fill = NOW  # the entries shifted in are not due by their timers
@@ -208,20 +165,10 @@ def case(nflows, mode_name, mode, due, table, ref, reps, warmup, inner):
 
     # ---- timing ------------------------------------------------------------------------------------
     row = {"nflows": nflows, "window": window, "mode": mode_name, "due": due, "emitted": e, "exact": exact, "slots": S, "acks": NACK}
+    # a unit of the split baseline is already nflows triples
+    calls = {name: (fn, max(1, inner // nflows) if name == "b" else inner) for name, fn in variants.items()}
     for how in ("graph", "back_to_back"):
-        units = {}
-        for name, fn in variants.items():
-            k = max(1, inner // nflows) if name == "b" else inner  # a unit of the split baseline is already nflows triples
-            many = (lambda fn=fn, k=k: [fn() for _ in range(k)])
-            units[name] = (graph_of(many).replay if how == "graph" else many, k)
-        names = sorted(units)
-        t = {name: [] for name in names}
-        for rep in range(warmup + reps):
-            for name in (names if rep % 2 == 0 else names[::-1]):
-                run, k = units[name]
-                ms = timed(run) / k
-                if rep >= warmup:
-                    t[name].append(ms)
+        t = B.sample(B.repeated(calls, how), reps, warmup, alternate=True)
         med = {name: float(np.median(v)) for name, v in t.items()}
         res = {"unit_ms": {name: stats(v) for name, v in t.items()},
                "flows_over_a": round(med["flows"] / med["a"], 4),
@@ -235,20 +182,14 @@ def case(nflows, mode_name, mode, due, table, ref, reps, warmup, inner):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=25)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = B.parser()
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--flows", default="1,64,1024,16384")
     ap.add_argument("--modes", default="selective,cumulative")
     ap.add_argument("--due", default="all,1pct")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tx_flows", "tx_flows_bench.json"))
+    B.add_out(ap, "tx_flows")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("tx_flows_bench: needs a GPU (no CPU fallback)")
-    if a.reps < 10:
-        raise SystemExit("tx_flows_bench: --reps must be at least 10")
-    assert W.LIB.wtp_init(0) == 0, W.LIB.wtp_last_error()
+    res = B.start("tx_flows_bench", a, min_reps=10)
     base = torch.empty(S * MAXP, dtype=torch.uint8, device="cuda")
     W.synth_fill(base, seed=0x7F10)
     ref = torch.empty((S, STRIDE), dtype=torch.uint8, device="cuda")
@@ -262,14 +203,10 @@ def main():
                 if name in a.modes.split(","):
                     rows.append(case(int(f), name, mode, due, (base, offs, lens), ref, a.reps, a.warmup, a.inner))
                     print(f"tx_flows_bench: nflows {f} {name} {due} done", file=sys.stderr, flush=True)
-    res = {"tool": "tx_flows_bench", "device": torch.cuda.get_device_name(0), "library": W.LIB.wtp_version().decode(),
-           "lib_path": os.path.relpath(W.LIB_PATH, ROOT), "reps": a.reps, "warmup": a.warmup, "inner": a.inner,
-           "unit": "restore the state; ingest; advance; build over all 64 Ki slots (b: nflows triples); ms per unit", "cases": rows}
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
+    res.update({"inner": a.inner,
+                "unit": "restore the state; ingest; advance; build over all 64 Ki slots (b: nflows triples); ms per unit",
+                "cases": rows})
+    B.write_result(res, a.out)
 
 
 if __name__ == "__main__":
