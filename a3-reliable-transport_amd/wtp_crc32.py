@@ -32,6 +32,11 @@ RX_MAX_FLOWS = 1 << 20        # WTP_RX_MAX_FLOWS
 RX_MAX_FLOW_SLOTS = 1 << 24   # WTP_RX_MAX_FLOW_SLOTS (nflows * window of accept_data_packets_flows)
 TX_MAX_FLOWS = 1 << 20        # WTP_TX_MAX_FLOWS
 TX_MAX_FLOW_SLOTS = 1 << 20   # WTP_TX_MAX_FLOW_SLOTS (nflows * window of the tx_*_flows calls)
+NO_FLOW = 0xFFFFFFFF          # WTP_NO_FLOW: d_flow of a datagram whose address has no connection
+CONN_KEY_BYTES, CONN_WAYS, CONN_MAX_BUCKETS = 16, 16, 1 << 20  # WTP_CONN_*
+# WTP_CTL_*: d_verdict of flows_control
+(CTL_NONE, CTL_OPENED, CTL_START_DUP, CTL_START_OTHER, CTL_REFUSED_FULL, CTL_REFUSED_BUCKET, CTL_CLOSED, CTL_END_STALE,
+ CTL_END_OTHER, CTL_END_BUSY) = range(10)
 
 
 class WtpError(RuntimeError):
@@ -82,6 +87,12 @@ def _load() -> tuple:
         "wtp_tx_advance_flows": (i32, [vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "wtp_tx_build_retransmit_var_flows": (i32, [vp, sz, vp, vp, sz, vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, sz,
                                                     u32, vp, vp, vp, vp, vp, sz, vp]),
+        "wtp_conn_table_bytes": (sz, [u32]),
+        "wtp_conn_bucket": (u32, [vp, u32]),
+        "wtp_flows_classify": (i32, [vp, sz, sz, vp, u32, vp, vp]),
+        "wtp_conn_scratch_bytes": (sz, [sz, u32]),
+        "wtp_flows_control": (i32, [vp, sz, vp, vp, sz, vp, vp, sz, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, sz, u32, vp, vp,
+                                    vp, vp, vp, vp, vp, sz, vp]),
         "wtp_crc32_combine": (u32, [u32, u32, u64]),
         "wtp_crc32_concat_work_bytes": (sz, [sz]),
         "wtp_crc32_concat": (i32, [vp, vp, u64, u64, sz, vp, sz, vp, vp]),
@@ -395,6 +406,52 @@ def tx_build_retransmit_var_flows(base, base_bytes: int, offsets, lengths, nrec:
 
 
 # ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------
+def conn_table_bytes(nbuckets: int) -> int:
+    """The size of a connection table of `nbuckets` buckets (wtp_conn_table_bytes): the caller
+    allocates it 16-B aligned and fills it with 0xFF bytes once."""
+    return int(LIB.wtp_conn_table_bytes(nbuckets))
+
+
+def conn_bucket(key, nbuckets: int) -> int:
+    """The bucket of a 16-byte key (wtp_conn_bucket): the hash the kernels use, on the host."""
+    key = bytes(key)
+    if len(key) != CONN_KEY_BYTES:
+        raise WtpError(f"a key is {CONN_KEY_BYTES} bytes, not {len(key)}")
+    return int(LIB.wtp_conn_bucket(key, nbuckets))
+
+
+def conn_scratch_bytes(n: int, nflows: int) -> int:
+    return int(LIB.wtp_conn_scratch_bytes(n, nflows))
+
+
+def flows_classify(keys, key_stride: int, n: int, table, nbuckets: int, flow, stream=None) -> None:
+    """The flow of every datagram of a batch by its source address (wtp_flows_classify): key i is
+    the 16 bytes at keys + i * key_stride; flow[i] (n x u32) = the flow whose connection has that
+    key in `table`, else NO_FLOW.  Only reads the table."""
+    _check(LIB.wtp_flows_classify(_dptr(keys), key_stride, n, _dptr(table), nbuckets, _dptr(flow), _stream(stream)),
+           "wtp_flows_classify")
+
+
+def flows_control(dgrams, stride: int, recv_len, keys, key_stride: int, flow, ok, n: int, table, nbuckets: int, nflows: int,
+                  window: int, flow_start, seq0, slot_len, free, free_pos, ack_wire, ack_stride: int, max_acks: int, ack_src,
+                  opened, opened_src, closed, verdict, counts, work=None, stream=None) -> None:
+    """Applies a batch's START and END datagrams to the connection table (wtp_flows_control), at
+    the end of the receive round: `flow` is flows_classify's result for the batch and `ok`
+    accept_data_packets_flows'.  A START of a new key takes the id at the head of the free ring
+    (free: nflows x u32, free_pos: {head, count}), maps the key to it and resets the flow
+    (flow_start = its seqNum, seq0 = 0, its slot_len EMPTY); an END of a drained flow frees the
+    entry and appends the id.  The answered datagrams become ACKs in `ack_wire` (ack_src: their
+    indices); opened / opened_src / closed list the events in arrival order, verdict (n x u32)
+    holds the CTL_* codes and counts (6 x u32) = {ACKs emitted, eligible, opened, closed,
+    refused full, refused bucket}.  ack_src, opened_src and verdict may be None."""
+    work, wp, wb = _work(work, conn_scratch_bytes(n, nflows))
+    _check(LIB.wtp_flows_control(_dptr(dgrams), stride, _dptr(recv_len), _dptr(keys), key_stride, _dptr(flow), _dptr(ok), n,
+                                 _dptr(table), nbuckets, nflows, window, _dptr(flow_start), _dptr(seq0), _dptr(slot_len),
+                                 _dptr(free), _dptr(free_pos), _dptr(ack_wire), ack_stride, max_acks, _dptr(ack_src),
+                                 _dptr(opened), _dptr(opened_src), _dptr(closed), _dptr(verdict), _dptr(counts), wp, wb,
+                                 _stream(stream)), "wtp_flows_control")
+
+
 def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
     """crc32(A || B) from crc32(A), crc32(B), len(B) (zlib crc32_combine; host, no device)."""
     return int(LIB.wtp_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, len_b))

@@ -892,6 +892,158 @@ int wtp_tx_build_retransmit_var_flows(const void *d_base, size_t base_bytes,
                                       uint32_t *d_sel, uint32_t *d_wire_len, uint32_t *d_crc_out,
                                       uint32_t *d_counts, void *d_work, size_t work_bytes, void *stream);
 
+/* ---- the connection table: classify by address, open and close flows -------------------
+   The layer in front of and behind the multi-flow receive round.  wtp_flows_classify makes
+   the round's d_flow from the datagrams' source addresses; wtp_flows_control, after
+   wtp_rx_advance_flows, applies the batch's START and END datagrams (cpp/src/wReceiver.cpp:
+   199-254, for one connection: ring.peer(k), open, start_seq, expected = 0): it opens flows,
+   closes flows and writes the control ACKs.  The round classify -> accept_flows ->
+   build_acks_flows -> deliver_flows -> advance_flows -> control is six stream-ordered calls
+   for any number of connections, those that come and go included, so one captured graph
+   serves every round and the host reads counters and two short event lists at its end.
+
+   The table.  d_table is opaque, caller-owned device memory of wtp_conn_table_bytes(nbuckets)
+   bytes (320 per bucket), 16-B aligned, which the caller fills with 0xFF bytes once: that
+   value means "empty", d_slot_len's convention.  nbuckets is a power of two in [1,
+   WTP_CONN_MAX_BUCKETS]; wtp_conn_table_bytes gives 0 for any other value.  A key is any
+   WTP_CONN_KEY_BYTES = 16 bytes (a sockaddr_in as recvmmsg writes msg_name): every one of the
+   2^128 values is a valid key, occupancy lives in a tag word beside the key.  A key belongs
+   to exactly one bucket, wtp_conn_bucket(key16, nbuckets) (host, pure, thread-safe, touches no
+   device; WTP_NO_FLOW for a NULL key or a bad nbuckets), the same function the kernels use.  A
+   bucket holds WTP_CONN_WAYS live connections in any order; a lookup scans one bucket and
+   nothing else (constant work, no probe chains), and freeing an entry is marking it empty
+   (no tombstones).  With nbuckets >= nflows / 2 a bucket's load is Poisson with mean <= 2 and
+   P(more than 16 in a bucket) is about 5.6e-11; at mean 4 it is 1.1e-6.
+
+   wtp_flows_classify: key i is the 16 bytes at d_keys + i*key_stride.  d_flow[i] = the flow
+   whose connection has that key, else WTP_NO_FLOW (every _flows call treats any value >=
+   nflows as "no connection").  It only reads the table and the keys and writes d_flow[0 .. n)
+   and nothing else; no byte outside [d_keys, d_keys + (n-1)*key_stride + 16) is loaded.  One
+   launch, one lane per datagram.  Fast path: a 16-B aligned key is one 16-B load, a 4-B
+   aligned key four dword loads; any other alignment loads bytewise.  n == 0 is valid and
+   launches nothing.  WTP_EINVAL (before any device is touched, each with its own message): n
+   >= 2^31; key_stride < 16; nbuckets zero, not a power of two or above the limit; a NULL
+   d_keys, d_table or d_flow with n > 0; d_table not 16-B aligned.  wtp_last_kernel() names
+   "k_conn_classify".
+
+   wtp_flows_control runs at the end of the receive round, on the same stream, with the same
+   batch (ring, d_recv_len, d_keys), accept's d_ok, classify's d_flow (a snapshot of the table
+   as it was on entry to the round; with any other d_flow the result is unspecified, though
+   no access leaves the caller's arrays) and the d_seq0 and d_slot_len that the advance
+   wrote, the next round's state.  d_recv_len is not read: d_ok says that the header is there.
+   Per-flow arrays: d_flow_start[nflows], the START seqNum of the flow's connection,
+   meaningful only while the flow is open; d_seq0[nflows] and d_slot_len[nflows*window],
+   accept_flows' state.  The free-id ring is d_free[nflows] and d_free_pos[2] = {head, count},
+   a FIFO: the caller initialises d_free[j] = j, head = 0, count = nflows; opens take ids from
+   the head, closes append at (head + count) mod nflows.  Popped and pushed cells are disjoint
+   by construction, so no launch reads and writes one cell.  The cells hold ids below nflows; one
+   that does not is never used as a flow (the open it would have served is refused), and that
+   call's d_counts and d_free_pos are unspecified.
+
+   Datagram i is a control datagram iff d_ok[i] != 0 and its type is START or END
+   (wtp_tx_ingest_acks' treatment of ACKs; stricter than the reference, which does not check
+   them).  Everything else gets the verdict WTP_CTL_NONE.  Stated sequentially: all STARTs are
+   processed in index (arrival) order, then all ENDs in index order; each is judged by f =
+   d_flow[i], the entry snapshot.
+   START, f < nflows (the key already has a connection): seqNum == d_flow_start[f] gives
+   WTP_CTL_START_DUP, answered (the START's ACK was lost), no state changes; otherwise
+   WTP_CTL_START_OTHER, dropped (opt/Receiver.cpp:148-150).
+   START, f >= nflows (a new key): the first such datagram of a key needs a free entry in its
+   bucket, else WTP_CTL_REFUSED_BUCKET, and then a free id, else WTP_CTL_REFUSED_FULL.  Neither
+   refusal is answered and neither changes state (an entry taken during the attempt is
+   released): the sender's START times out and comes again.  Otherwise WTP_CTL_OPENED,
+   answered: with g = the id at the ring's head, the table maps the key to g, d_flow_start[g] =
+   seqNum, d_seq0[g] = 0 (the endpoints' expected = 0) and d_slot_len[g*window .. +window) =
+   WTP_SLOT_EMPTY.  A later datagram with the same new key in the same batch is judged
+   against what the first one did: START_DUP or START_OTHER by its seqNum if the first
+   opened, the first's refusal verdict otherwise.  Flow ids are therefore deterministic: the
+   r-th connection opened in arrival order gets the r-th id of the ring.  With nflows == 0
+   the table is not looked at and every START is REFUSED_FULL.
+   END, f >= nflows: WTP_CTL_END_STALE, answered (the duplicate END of a connection already
+   closed, wReceiver.cpp:219-221, or an END with no connection).  f < nflows and seqNum !=
+   d_flow_start[f]: WTP_CTL_END_OTHER, dropped.  f < nflows, seqNum equal, window > 0 and
+   d_slot_len[f*window] != WTP_SLOT_EMPTY: WTP_CTL_END_BUSY, dropped (the flow still holds
+   undelivered data, the stream cut fell before it; the sender's END comes again; only slot 0
+   is looked at).  Otherwise the first such datagram of flow f is WTP_CTL_CLOSED, answered:
+   the key's entry is freed and f is appended to the ring; the flow's window is not touched
+   (the next open resets it).  Later such ENDs of f in the batch are END_STALE, answered.  A
+   flow opened in this call cannot be closed in it (its datagrams carry WTP_NO_FLOW), so opens
+   and closes are independent within a call, and an entry or an id freed in a call serves no
+   open of that call.
+
+   Determinism and overflow.  The result is exactly the sequential statement's whenever no
+   bucket overflows in the call: live entries plus distinct new keys hashing to the bucket
+   exceed WTP_CONN_WAYS.  On overflow: the number opened into the bucket is exactly its free
+   entries, further limited by the free ids, in arrival order among the keys that hold an
+   entry; the remaining keys are refused and nothing of theirs is left in the table;
+   everything outside that bucket's new keys is exact.  Which keys of the bucket are refused,
+   and REFUSED_BUCKET against REFUSED_FULL when both are short, is unspecified.
+
+   Outputs.  The answered datagrams are ranked in arrival order across both kinds; rank k <
+   max_acks becomes d_ack_wire[k*ack_stride .. +16) = htonl{3, the datagram's own seqNum, 0, 0}
+   and d_ack_src[k] = i: one 16-B store where the slot is 16-B aligned, bytes otherwise.  State
+   changes are applied whether or not the ACK fits: a peer whose ACK was cut retransmits and
+   gets START_DUP or END_STALE.  d_opened[r], d_opened_src[r] = the flow and the datagram index
+   of the r-th open, d_closed[q] = the q-th closed flow, in arrival order; each list has at
+   most nflows entries.  d_verdict[i] = the WTP_CTL_* code.  d_ack_src, d_opened_src and
+   d_verdict may be NULL.  d_counts[0 .. 6) = {ACKs emitted, ACKs eligible, opened, closed,
+   datagrams refused full, datagrams refused bucket}, always written, also for n == 0, nflows
+   == 0 and max_acks == 0, which are all valid.  d_free_pos = {head + opened mod nflows, count
+   - opened + closed}.  Nothing else is written: entries past the counts and bytes [16,
+   ack_stride) of a slot stay as they were; d_seq0, d_flow_start and d_slot_len of flows not
+   opened stay as they were; ring cells neither popped nor pushed stay as they were; every
+   input is only read.  While the call runs a table tag may hold a claim (0x80000000 |
+   datagram index, d_slot_len's encoding); a completed call leaves none behind.
+
+   d_work is the caller's scratch (any alignment, contents arbitrary on entry, unspecified on
+   return; every word the call reads it has written before).  wtp_conn_scratch_bytes(n, nflows)
+   = 20 + 4*n + 12*ceil(n / 1024) + 8*nflows (its arguments clamped to the limits), monotone in
+   both arguments and at most 64 KiB + 8 bytes per datagram + 8 bytes per flow.
+   WTP_EINVAL (before any device is touched, each with its own message): n >= 2^31; stride <
+   16; key_stride < 16; ack_stride < 16; a bad nbuckets; nflows > WTP_RX_MAX_FLOWS, window >
+   WTP_RX_MAX_WINDOW, nflows*window > WTP_RX_MAX_FLOW_SLOTS; work_bytes too small; a NULL
+   d_counts or d_work; a NULL d_table, d_flow_start, d_seq0, d_free, d_free_pos, d_opened or
+   d_closed with nflows > 0; a NULL d_slot_len with nflows*window > 0; a NULL d_dgrams,
+   d_recv_len, d_ok, d_keys or d_flow with n > 0; a NULL d_ack_wire with n > 0 and max_acks >
+   0; d_table not 16-B aligned.
+   Stream-ordered launches (mark and claim, count, open, close, emit, reset) with no host
+   synchronisation, no allocation and no library table, so no wtp_init is needed before a
+   capture; grids are sized from n, nflows and window, never from device values, and nothing
+   is serial per datagram or per flow: a batch of 64 Ki STARTs is the same kind of work as
+   one START.  Graph captures, replays and concurrent calls on different tables, states and
+   work buffers are independent.  wtp_last_kernel() names "k_conn_reset", or "k_conn_emit"
+   when n == 0 or nflows*window == 0 and no slot can be reset. */
+#define WTP_NO_FLOW          0xFFFFFFFFu
+#define WTP_CONN_KEY_BYTES   16u
+#define WTP_CONN_WAYS        16u
+#define WTP_CONN_MAX_BUCKETS (1u << 20)
+#define WTP_CTL_NONE           0u
+#define WTP_CTL_OPENED         1u
+#define WTP_CTL_START_DUP      2u
+#define WTP_CTL_START_OTHER    3u
+#define WTP_CTL_REFUSED_FULL   4u
+#define WTP_CTL_REFUSED_BUCKET 5u
+#define WTP_CTL_CLOSED         6u
+#define WTP_CTL_END_STALE      7u
+#define WTP_CTL_END_OTHER      8u
+#define WTP_CTL_END_BUSY       9u
+size_t wtp_conn_table_bytes(uint32_t nbuckets);
+uint32_t wtp_conn_bucket(const void *key16, uint32_t nbuckets);
+int wtp_flows_classify(const void *d_keys, size_t key_stride, size_t n,
+                       const void *d_table, uint32_t nbuckets,
+                       uint32_t *d_flow, void *stream);
+size_t wtp_conn_scratch_bytes(size_t n, uint32_t nflows);
+int wtp_flows_control(const void *d_dgrams, size_t stride, const uint32_t *d_recv_len,
+                      const void *d_keys, size_t key_stride, const uint32_t *d_flow,
+                      const uint8_t *d_ok, size_t n,
+                      void *d_table, uint32_t nbuckets, uint32_t nflows, uint32_t window,
+                      uint32_t *d_flow_start, uint32_t *d_seq0, uint32_t *d_slot_len,
+                      uint32_t *d_free, uint32_t *d_free_pos,
+                      void *d_ack_wire, size_t ack_stride, uint32_t max_acks, uint32_t *d_ack_src,
+                      uint32_t *d_opened, uint32_t *d_opened_src, uint32_t *d_closed,
+                      uint32_t *d_verdict, uint32_t *d_counts,
+                      void *d_work, size_t work_bytes, void *stream);
+
 /* ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------
    The reference's crc32(buf, size) takes any size; these give it for device-resident data
    of any size from the per-chunk CRCs, by zlib's crc32_combine identity
