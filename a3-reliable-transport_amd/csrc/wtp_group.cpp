@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "wtp_device_scope.hpp"
 #include "wtp_group.h"
 
 extern "C" int wtp_set_error_(int code, const char *msg);
@@ -20,17 +21,6 @@ struct wtp_group {
 namespace {
 
 int gfail(int code, const std::string &m) { return wtp_set_error_(code, m.c_str()); }
-
-// Runs f with device d current, then restores the caller's device.
-template <class F>
-int on_device(int d, F &&f) {
-    int prev = 0;
-    if (hipGetDevice(&prev) != hipSuccess) return gfail(WTP_EHIP, "hipGetDevice failed");
-    if (hipSetDevice(d) != hipSuccess) return gfail(WTP_ENODEV, "hipSetDevice(" + std::to_string(d) + ") failed");
-    const int rc = f();
-    (void)hipSetDevice(prev);
-    return rc;
-}
 
 int nccl_fail(const char *what, ncclResult_t r) {
     return gfail(WTP_EHIP, std::string(what) + ": " + ncclGetErrorString(r));
@@ -54,10 +44,8 @@ int wtp_group_create(const int *devices, int ndev, wtp_group **out) {
         }
     }
     g->comm.resize(ndev);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
+    const wtp::DeviceScope keep;  // ncclCommInitAll leaves another device current
     const ncclResult_t r = ncclCommInitAll(g->comm.data(), ndev, g->dev.data());
-    (void)hipSetDevice(prev);
     if (r != ncclSuccess) {
         delete g;
         return nccl_fail("ncclCommInitAll", r);
@@ -85,13 +73,17 @@ int wtp_group_crc32_fixed_gather(wtp_group *g, const void *const *d_shards, size
     for (int r = 0; r < R; ++r)
         if (!d_local[r] || (n_per[r] && !d_shards[r])) return gfail(WTP_EINVAL, "null shard or result pointer");
     auto st = [&](int r) { return streams ? static_cast<hipStream_t>(streams[r]) : hipStream_t(nullptr); };
+    wtp::DeviceScope scope;  // every exit below leaves the caller's device current
+    if (!scope.ok()) return gfail(WTP_EHIP, "hipGetDevice failed");
+    auto use = [&](int r) {
+        return scope.use(g->dev[r]) ? int(WTP_OK)
+                                    : gfail(WTP_ENODEV, "hipSetDevice(" + std::to_string(g->dev[r]) + ") failed");
+    };
+    int rc = WTP_OK;
     // 1. every rank checksums its shard (the braided kernel for 1456-B payloads)
-    for (int r = 0; r < R; ++r) {
-        const int rc = on_device(g->dev[r], [&] {
-            return wtp_crc32_batch_fixed(d_shards[r], stride, len, n_per[r], d_local[r], st(r));
-        });
-        if (rc) return rc;
-    }
+    for (int r = 0; r < R; ++r)
+        if ((rc = use(r)) || (rc = wtp_crc32_batch_fixed(d_shards[r], stride, len, n_per[r], d_local[r], st(r))))
+            return rc;
     // 2. gather to the root, stream-ordered after each rank's kernel.  Every device is
     // made current once before the group opens, so nothing expected can fail between
     // ncclGroupStart and ncclGroupEnd; if an enqueue still fails there, the ops already
@@ -99,20 +91,14 @@ int wtp_group_crc32_fixed_gather(wtp_group *g, const void *const *d_shards, size
     // communicators are aborted (and the group refuses further use) instead.
     bool equal = true;
     for (int r = 1; r < R; ++r) equal = equal && n_per[r] == n_per[0];
-    int prev = 0;
-    (void)hipGetDevice(&prev);
     for (int r = 0; r < R; ++r)
-        if (hipSetDevice(g->dev[r]) != hipSuccess) {
-            (void)hipSetDevice(prev);
-            return gfail(WTP_ENODEV, "hipSetDevice(" + std::to_string(g->dev[r]) + ") failed");
-        }
+        if ((rc = use(r))) return rc;
     ncclResult_t res = ncclGroupStart();
     if (res != ncclSuccess) return nccl_fail("ncclGroupStart", res);
-    int rc = WTP_OK;
     size_t off_root = 0;
     for (int r = 0; r < root; ++r) off_root += n_per[r];
     for (int r = 0; r < R && rc == WTP_OK; ++r) {
-        if (hipSetDevice(g->dev[r]) != hipSuccess) {
+        if (!scope.use(g->dev[r])) {
             rc = gfail(WTP_ENODEV, "hipSetDevice failed");
             break;
         }
@@ -138,16 +124,14 @@ int wtp_group_crc32_fixed_gather(wtp_group *g, const void *const *d_shards, size
     if (rc != WTP_OK) {
         for (ncclComm_t c : g->comm) (void)ncclCommAbort(c);
         g->aborted = true;
-        (void)hipSetDevice(prev);
         return rc;
     }
     // the root's own shard (ragged path): a device-local copy behind its kernel
-    if (rc == WTP_OK && !equal && n_per[root] && hipSetDevice(g->dev[root]) == hipSuccess) {
+    if (!equal && n_per[root] && scope.use(g->dev[root])) {
         if (hipMemcpyAsync(d_out + off_root, d_local[root], n_per[root] * 4, hipMemcpyDeviceToDevice, st(root)) !=
             hipSuccess)
             rc = gfail(WTP_EHIP, "hipMemcpyAsync (root shard) failed");
     }
-    (void)hipSetDevice(prev);
     return rc;
 }
 

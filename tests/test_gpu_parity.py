@@ -1496,6 +1496,52 @@ def test_host_verify_pinned_small_batches(W, zero_copy, n, stride, skip):
     lens.free()
 
 
+@pytest.fixture(scope="module")
+def three_slab_ring():
+    """(ring, lengths, want_ok, want_crc) of 2 * 45590 + 1 datagrams at stride 1472: two whole
+    64 MiB slabs of the host verify's copy pipeline and a third slab of one datagram, so
+    buffer 0 is issued again while slab 1 is live.  A 1013-datagram ring tiled (1013 does not
+    divide 45590: the slab edges fall inside a tile) and the oracle's answer tiled with it,
+    then one payload bit flipped on either side of the first slab edge and in the third slab,
+    those three datagrams through the oracle on their own."""
+    stride, per, tile = 1472, (64 << 20) // 1472, 1013
+    n = 2 * per + 1
+    assert per == 45590 and n == 91181 and per % tile
+    buf1, rl1 = _full_ring(tile, stride, np.random.default_rng(77), 0.85)
+    ok1, crc1 = O.verify_datagrams(buf1, stride, rl1)
+    reps = -(-n // tile)
+    buf = np.tile(buf1, reps)[:n * stride]
+    rl, want_ok, want_crc = (np.tile(a, reps)[:n].copy() for a in (rl1, ok1, crc1))
+    for i in (per - 1, per, n - 1):
+        assert want_ok[i] == 1 and rl[i] > 16 + 700  # a good datagram, so the flip must show
+        buf[i * stride + 16 + 700] ^= 8
+        o, c = O.verify_datagrams(buf[i * stride:(i + 1) * stride], stride, rl[i:i + 1])
+        assert o[0] == 0
+        want_ok[i], want_crc[i] = o[0], c[0]
+    return buf, rl, want_ok, want_crc
+
+
+@pytest.mark.parametrize("pinned", [False, True])
+def test_host_verify_three_slabs(W, three_slab_ring, pinned):
+    """The host verify's copy pipeline through its third slab, from pageable and from pinned
+    memory, ok and crc element-wise (the other host verify tests stay within two slabs)."""
+    buf, rl, want_ok, want_crc = three_slab_ring
+    n, stride = rl.size, 1472
+    bufs = []
+    if pinned:
+        ring, lens = W.PinnedBuffer(n * stride), W.PinnedBuffer(n * 4)
+        bufs = [ring, lens]
+        ring.array[:] = buf
+        lens.array.view(np.uint32)[:] = rl
+        ok, crc = W.host_verify(ring.array, stride, lens.array.view(np.uint32))
+    else:
+        ok, crc = W.host_verify(buf, stride, rl)
+    bad_ok, bad_crc = np.nonzero(ok != want_ok)[0], np.nonzero(crc != want_crc)[0]
+    for b in bufs:
+        b.free()
+    assert bad_ok.size == 0 and bad_crc.size == 0, (bad_ok[:5], bad_crc[:5])
+
+
 def test_build_data_packets(W):
     for total in (64, 1456, 2216, 10202, 1456 * 300 + 17):
         host = O.synth_fill_np(total, start_byte=total)
@@ -1559,6 +1605,8 @@ def test_build_data_packets_paths(W, total, stride, pay_off, wire_off, with_len,
     (1456 * 10 + 1, 1500, False, True, True, 1),         # stride % 16 != 0: the three-step path
     (100, 1472, True, True, True, 0),                    # one short datagram
     (1456 * 100 + 5, 1500, True, True, True, 7),         # zero copy into 1500-B slots: the three-step path over host memory
+    (1456 * 91180 + 1, 1472, False, False, True, 5),     # three slabs (45590, 45590, 1), the last a single 1-B chunk
+    (1456 * 91180 + 1, 1472, True, True, True, 5),       # the same pinned: through the slabs when zero_copy == "0"
 ])
 @pytest.mark.parametrize("zero_copy", ["1", "0"])
 def test_host_build_data_packets(W, total, stride, pin_src, pin_wire, with_len, seq0, zero_copy):
