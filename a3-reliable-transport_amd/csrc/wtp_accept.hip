@@ -14,7 +14,8 @@
 //                    filled and the lowest index wins; the window state itself is the
 //                    only scratch.
 //   3. k_accept_place 16 lanes per datagram: the owner (slot_len[s] == 0x80000000 | i)
-//                    copies its payload, then publishes slot_len[s] = len and place[i];
+//                    copies its payload (wtp_common.hpp: copy_slot16), then publishes
+//                    slot_len[s] = len and place[i];
 //                    every lane also scans its share of slot_len for the first EMPTY slot
 //                    (the cumulative ACK).
 //
@@ -37,20 +38,6 @@
 namespace wtp {
 namespace dev {
 
-constexpr uint32_t kClaim = 0x80000000u;  // claim of datagram i = kClaim | i (n < 2^31)
-constexpr uint32_t kGroup = 16;           // lanes per datagram in k_accept_place
-constexpr uint32_t kVecs = (WTP_MAX_PAYLOAD / 16 + kGroup - 1) / kGroup;  // 91 vectors -> 6 per lane
-
-__device__ __forceinline__ u32x4 ld16(const u32x4 *p) {
-    return WTP_ACCEPT_LNT ? __builtin_nontemporal_load(p) : *p;
-}
-__device__ __forceinline__ void st16(u32x4 *p, u32x4 v) {
-    if (WTP_ACCEPT_NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
-
 // Slot of datagram i if it may be placed (intact, DATA, payload <= 1456 B, inside the
 // window), else WTP_NOT_PLACED.  ok[i] != 0 already says 16 <= recv_len <= stride.
 __device__ __forceinline__ uint32_t accept_slot(const uint8_t *__restrict__ ring, uint64_t stride,
@@ -64,17 +51,6 @@ __device__ __forceinline__ uint32_t accept_slot(const uint8_t *__restrict__ ring
     len = rl - WTP_HEADER_BYTES;
     const uint32_t s = seq - seq0;  // unsigned: wrap is well defined
     return len <= WTP_MAX_PAYLOAD && type == WTP_TYPE_DATA && s < window ? s : WTP_NOT_PLACED;
-}
-
-// The ACK is kept as seq0 + (lowest EMPTY slot seen so far); "lower" is taken on the slot
-// index, i.e. after subtracting seq0, so a window that wraps 2^32 orders correctly.
-__device__ __forceinline__ void ack_lower(uint32_t *ack, uint32_t seq0, uint32_t s) {
-    uint32_t cur = __hip_atomic_load(ack, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (s < cur - seq0) {
-        const uint32_t seen = atomicCAS(ack, cur, seq0 + s);
-        if (seen == cur) break;
-        cur = seen;
-    }
 }
 
 __global__ void __launch_bounds__(256)
@@ -119,32 +95,8 @@ k_accept_place(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t
     }
     const uint8_t *src = ring + i * stride + WTP_HEADER_BYTES;
     uint8_t *dst = out + uint64_t(s) * WTP_MAX_PAYLOAD;
-    if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0) {
-        const u32x4 *vs = reinterpret_cast<const u32x4 *>(src);
-        u32x4 *vd = reinterpret_cast<u32x4 *>(dst);
-        const uint32_t nvec = len / 16;
-        if (len == WTP_MAX_PAYLOAD) {
-            // a full packet, 91 vectors: rows 0 .. 4 whole, row 5 lanes 0 .. 10; all of a
-            // lane's loads are in flight before its first store
-            u32x4 w[kVecs];
-#pragma unroll
-            for (uint32_t k = 0; k + 1 < kVecs; ++k) w[k] = ld16(vs + g + k * kGroup);
-            const bool last = g + (kVecs - 1) * kGroup < WTP_MAX_PAYLOAD / 16;
-            if (last) w[kVecs - 1] = ld16(vs + g + (kVecs - 1) * kGroup);
-#pragma unroll
-            for (uint32_t k = 0; k + 1 < kVecs; ++k) st16(vd + g + k * kGroup, w[k]);
-            if (last) st16(vd + g + (kVecs - 1) * kGroup, w[kVecs - 1]);
-        } else {
-#pragma clang loop unroll_count(2)
-            for (uint32_t v = g; v < nvec; v += kGroup) st16(vd + v, ld16(vs + v));
-        }
-        const uint32_t b = nvec * 16 + g;  // byte-exact tail: at most 15 bytes, one per lane
-        if (b < len) dst[b] = src[b];
-    } else {
-        // any other alignment: bytes (exact; no access wider than the buffers' alignment)
-#pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
-        for (uint32_t b = g; b < len; b += kGroup) dst[b] = src[b];
-    }
+    const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0;
+    copy_slot16<WTP_ACCEPT_LNT, WTP_ACCEPT_NT>(src, dst, len, g, vec);
     if (g == 0) {
         slot_len[s] = len;
         if (place) place[i] = s;

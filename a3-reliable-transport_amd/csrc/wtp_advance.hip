@@ -23,6 +23,8 @@
 //                 Images that are not both 16-B aligned move byte by byte.
 //   k_tx_advance  one lane per entry of both arrays.
 // No LDS, no atomics, no scratch, no library table; *d_adv is one uniform load.
+// k_rx_advance keeps its own copy of the slot copy's text (wtp_common.hpp: copy_slot16): on the
+// helper its machine code changed and the timing rule did not let it move.
 //
 // A separate translation unit: see wtp_common.hpp.
 #include <algorithm>
@@ -39,9 +41,6 @@ namespace dev {
 constexpr uint32_t kAdvBlock = 256;  // four waves, each on its own rounds
 constexpr uint32_t kAdvWaves = kAdvBlock / 64;
 constexpr uint32_t kAdvMaxBlocks = 2048;  // the capped grid: eight workgroups per CU, 2^19 slots per pass
-constexpr uint32_t kAdvGroup = 16;        // lanes per slot
-constexpr uint32_t kAdvVecs = (WTP_MAX_PAYLOAD / 16 + kAdvGroup - 1) / kAdvGroup;  // 91 vectors -> 6 per lane
-static_assert(WTP_MAX_PAYLOAD % 16 == 0, "every slot of a 16-B aligned image is 16-B aligned");
 static_assert(uint64_t(WTP_RX_MAX_WINDOW) * 2 < (uint64_t(1) << 32), "s + a fits 32 bits");
 
 __device__ __forceinline__ void adv_store(u32x4 *p, u32x4 v) {
@@ -59,7 +58,7 @@ k_rx_advance(const uint8_t *__restrict__ img, const uint32_t *__restrict__ slot_
              uint32_t vec) {
     const uint64_t by = *adv;
     const uint32_t a = by < window ? uint32_t(by) : window;
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x / 64, g = lane % kAdvGroup, q = lane / kAdvGroup;
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x / 64, g = lane % kGroup, q = lane / kGroup;
     const uint32_t rounds = (window + 63) / 64, step = gridDim.x * kAdvWaves;
     for (uint32_t r = blockIdx.x * kAdvWaves + wv; r < rounds; r += step) {
         const uint32_t s = r * 64 + lane;
@@ -74,7 +73,7 @@ k_rx_advance(const uint8_t *__restrict__ img, const uint32_t *__restrict__ slot_
         while (todo) {
             uint32_t pick = 64;
 #pragma unroll
-            for (uint32_t j = 0; j < 64 / kAdvGroup; ++j) {
+            for (uint32_t j = 0; j < 64 / kGroup; ++j) {
                 const uint32_t b = todo ? uint32_t(__builtin_ctzll(todo)) : 64u;
                 todo &= todo - 1;
                 if (q == j) pick = b;
@@ -91,25 +90,25 @@ k_rx_advance(const uint8_t *__restrict__ img, const uint32_t *__restrict__ slot_
                 if (len == WTP_MAX_PAYLOAD) {
                     // a full slot, 91 vectors: rows 0 .. 4 whole, row 5 lanes 0 .. 10; all of a
                     // lane's loads are in flight before its first store
-                    u32x4 w[kAdvVecs];
+                    u32x4 w[kSlotVecs];
 #pragma unroll
-                    for (uint32_t k = 0; k + 1 < kAdvVecs; ++k) w[k] = vs[g + k * kAdvGroup];
-                    const bool last = g + (kAdvVecs - 1) * kAdvGroup < WTP_MAX_PAYLOAD / 16;
-                    if (last) w[kAdvVecs - 1] = vs[g + (kAdvVecs - 1) * kAdvGroup];
+                    for (uint32_t k = 0; k + 1 < kSlotVecs; ++k) w[k] = vs[g + k * kGroup];
+                    const bool last = g + (kSlotVecs - 1) * kGroup < WTP_MAX_PAYLOAD / 16;
+                    if (last) w[kSlotVecs - 1] = vs[g + (kSlotVecs - 1) * kGroup];
 #pragma unroll
-                    for (uint32_t k = 0; k + 1 < kAdvVecs; ++k) adv_store(vd + g + k * kAdvGroup, w[k]);
-                    if (last) adv_store(vd + g + (kAdvVecs - 1) * kAdvGroup, w[kAdvVecs - 1]);
+                    for (uint32_t k = 0; k + 1 < kSlotVecs; ++k) adv_store(vd + g + k * kGroup, w[k]);
+                    if (last) adv_store(vd + g + (kSlotVecs - 1) * kGroup, w[kSlotVecs - 1]);
                 } else {
                     // a shorter one: a Zipf record is a vector or two per lane
 #pragma clang loop unroll_count(2)
-                    for (uint32_t x = g; x < nvec; x += kAdvGroup) adv_store(vd + x, vs[x]);
+                    for (uint32_t x = g; x < nvec; x += kGroup) adv_store(vd + x, vs[x]);
                 }
                 const uint32_t b = nvec * 16 + g;  // byte-exact tail: at most 15 bytes, one per lane
                 if (b < len) dst[b] = src[b];
             } else {
                 // any other alignment: bytes (exact; no access wider than the images' alignment)
 #pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
-                for (uint32_t b = g; b < len; b += kAdvGroup) dst[b] = src[b];
+                for (uint32_t b = g; b < len; b += kGroup) dst[b] = src[b];
             }
         }
     }

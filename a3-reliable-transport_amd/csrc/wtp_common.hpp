@@ -1,6 +1,7 @@
 // wtp_common.hpp — what the protocol translation units (PROTO in the Makefile) share: on the
 // host the error plumbing, the launch helper, the argument checks and the d_work layout, and
-// on the device the header's wire format, the wave reductions and a few one-line helpers.
+// on the device the header's wire format, the wave reductions, a few one-line helpers, the
+// receive window's claim, ACK and slot copy, and the flush kernels' owner searches.
 // Internal: the C-ABI is include/wtp_crc32.h.
 //
 // Each protocol call is a separate translation unit: k_fixed_braid and everything it
@@ -180,9 +181,116 @@ __device__ __forceinline__ u32x4 header_be(uint32_t type, uint32_t seq, uint32_t
     return hv;
 }
 
+// An ACK datagram at slot: htonl{type = 3, seqNum, length = 0, checksum = crc32("") = 0}.
+__device__ __forceinline__ void store_ack(uint8_t *slot, uint32_t seq) {
+    if ((reinterpret_cast<uintptr_t>(slot) & 15u) == 0) {  // one 16-B store
+        *reinterpret_cast<u32x4 *>(slot) = header_be(WTP_TYPE_ACK, seq, 0u, 0u);
+    } else {
+        // any other alignment: bytes (no access wider than the slot's alignment)
+        // the loop stays rolled, or the compiler merges the sixteen stores into one
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+        for (uint32_t b = 0; b < WTP_HEADER_BYTES; ++b) {
+            const uint32_t word = b < 4 ? uint32_t(WTP_TYPE_ACK) : b < 8 ? seq : 0u;
+            slot[b] = uint8_t(word >> (8 * (3 - b % 4)));
+        }
+    }
+}
+
+// ---- the receive window: slot_len claims, the cumulative ACK, the slot copy ---------------
+
+constexpr uint32_t kClaim = 0x80000000u;  // claim of datagram i = kClaim | i (n < 2^31)
+constexpr uint32_t kGroup = 16;           // lanes per slot (or datagram) in the place and advance kernels
+constexpr uint32_t kSlotVecs = (WTP_MAX_PAYLOAD / 16 + kGroup - 1) / kGroup;  // a full slot: 91 vectors -> 6 per lane
+static_assert(WTP_MAX_PAYLOAD % 16 == 0, "every slot of a 16-B aligned image is 16-B aligned");
+
+// The ACK is kept as seq0 + (lowest EMPTY slot seen so far); "lower" is taken on the slot
+// index, i.e. after subtracting seq0, so a window that wraps 2^32 orders correctly.
+__device__ __forceinline__ void ack_lower(uint32_t *ack, uint32_t seq0, uint32_t s) {
+    uint32_t cur = __hip_atomic_load(ack, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (s < cur - seq0) {
+        const uint32_t seen = atomicCAS(ack, cur, seq0 + s);
+        if (seen == cur) break;
+        cur = seen;
+    }
+}
+
+// Lane g of a 16-lane group copies its share of the len <= 1456 payload bytes of one slot.
+// vec (both ends 16-B aligned): floor(len / 16) vectors and a tail of one byte per lane.  A
+// full slot is 91 vectors, rows 0 .. 4 whole and row 5 lanes 0 .. 10, six per lane with all
+// of a lane's loads in flight before its first store; a shorter one (a Zipf record is a
+// vector or two per lane) a loop.  Any other alignment: bytes (exact; no access wider than
+// the buffers' alignment).  LNT / SNT: the 16-B loads / stores stream (nt).
+template <bool LNT, bool SNT>
+__device__ __forceinline__ void copy_slot16(const uint8_t *src, uint8_t *dst, uint32_t len, uint32_t g, bool vec) {
+    auto ld16 = [](const u32x4 *p) { return LNT ? __builtin_nontemporal_load(p) : *p; };
+    auto st16 = [](u32x4 *p, u32x4 v) {
+        if (SNT)
+            __builtin_nontemporal_store(v, p);
+        else
+            *p = v;
+    };
+    if (vec) {
+        const u32x4 *vs = reinterpret_cast<const u32x4 *>(src);
+        u32x4 *vd = reinterpret_cast<u32x4 *>(dst);
+        const uint32_t nvec = len / 16;
+        if (len == WTP_MAX_PAYLOAD) {
+            u32x4 w[kSlotVecs];
+#pragma unroll
+            for (uint32_t k = 0; k + 1 < kSlotVecs; ++k) w[k] = ld16(vs + g + k * kGroup);
+            const bool last = g + (kSlotVecs - 1) * kGroup < WTP_MAX_PAYLOAD / 16;
+            if (last) w[kSlotVecs - 1] = ld16(vs + g + (kSlotVecs - 1) * kGroup);
+#pragma unroll
+            for (uint32_t k = 0; k + 1 < kSlotVecs; ++k) st16(vd + g + k * kGroup, w[k]);
+            if (last) st16(vd + g + (kSlotVecs - 1) * kGroup, w[kSlotVecs - 1]);
+        } else {
+#pragma clang loop unroll_count(2)
+            for (uint32_t v = g; v < nvec; v += kGroup) st16(vd + v, ld16(vs + v));
+        }
+        const uint32_t b = nvec * 16 + g;  // byte-exact tail: at most 15 bytes, one per lane
+        if (b < len) dst[b] = src[b];
+    } else {
+#pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
+        for (uint32_t b = g; b < len; b += kGroup) dst[b] = src[b];
+    }
+}
+
+// ---- the flush kernels' search in a monotone prefix-sum array -------------------------------
+
+// The last index in [lo, hi] whose p is <= b (p(lo) <= b is the caller's).
+template <class Get>
+__device__ __forceinline__ uint32_t owner(Get p, uint32_t lo, uint32_t hi, uint32_t b) {
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (p(mid) <= b)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// The same over P[0 .. k] by a half-wave at a time: lanes 0 .. 31 look for one byte, lanes 32 ..
+// 63 for another, 32 probes per step, so 2^20 entries take four dependent loads and 2^24 five,
+// not twenty and more.  All 64 lanes call it; returns the half's answer in each of its lanes.
+template <class T>
+__device__ __forceinline__ uint32_t owner_wave(const T *__restrict__ P, uint32_t k, T b, uint32_t lane) {
+    uint32_t lo = 0, hi = k;
+    while (__ballot(lo < hi) != 0) {
+        const uint32_t step = max((hi - lo + 31) / 32, 1u);
+        const uint32_t idx = lo + ((lane & 31u) + 1) * step;  // <= 2^24 + 2^24 + 32
+        const bool le = idx <= hi && P[idx] <= b;             // P is monotone: true in a prefix of the half
+        const uint64_t bal = __ballot(le);
+        const uint32_t c = __popc(lane < 32 ? uint32_t(bal) : uint32_t(bal >> 32));
+        lo += c * step;
+        hi = min(hi, lo + step - 1);
+    }
+    return lo;
+}
+
 // The ordered compaction of k_tx_count / k_tx_select and k_ack_mark / k_ack_emit is not
 // here: as functions of this header its two halves did not leave those kernels' register
-// use and timing within the parent's, so each keeps its own body.
+// use and timing within the parent's, so each keeps its own body.  By the same
+// rule k_rx_advance and k_rx_advance_flows keep their copies of copy_slot16's text.
 
 }  // namespace dev
 }  // namespace wtp

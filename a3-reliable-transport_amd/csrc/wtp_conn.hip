@@ -387,19 +387,7 @@ k_conn_emit(const uint8_t *__restrict__ ring, uint64_t stride, uint32_t n, uint3
     if (verdict) verdict[i] = v;
     if (!ans || k >= max_acks) return;
     const uint32_t seq = load_header(ring + uint64_t(i) * stride).seq;
-    // htonl{type = 3, the datagram's own seqNum, length = 0, checksum = crc32("") = 0}
-    uint8_t *slot = wire + uint64_t(k) * ack_stride;
-    if ((reinterpret_cast<uintptr_t>(slot) & 15u) == 0) {  // one 16-B store
-        *reinterpret_cast<u32x4 *>(slot) = header_be(WTP_TYPE_ACK, seq, 0u, 0u);
-    } else {
-        // any other alignment: bytes (no access wider than the slot's alignment)
-        // the loop stays rolled, or the compiler merges the sixteen stores into one
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-        for (uint32_t b = 0; b < WTP_HEADER_BYTES; ++b) {
-            const uint32_t word = b < 4 ? uint32_t(WTP_TYPE_ACK) : b < 8 ? seq : 0u;
-            slot[b] = uint8_t(word >> (8 * (3 - b % 4)));
-        }
-    }
+    store_ack(wire + uint64_t(k) * ack_stride, seq);  // the datagram's own seqNum
     if (src) src[k] = i;
 }
 

@@ -165,36 +165,6 @@ k_deliver_scan(const uint32_t *__restrict__ slot_len, uint32_t window, uint32_t 
     }
 }
 
-// The last index in [lo, hi] whose P is <= b (P[lo] <= b is the caller's); p(i) = P[i].
-template <class Get>
-__device__ __forceinline__ uint32_t dl_owner(Get p, uint32_t lo, uint32_t hi, uint32_t b) {
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (p(mid) <= b)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
-// The same over [0, k] by a half-wave at a time: lanes 0 .. 31 look for b_first, lanes 32 ..
-// 63 for b_last, 32 probes per step, so 2^20 entries take four dependent loads, not twenty.
-// All 64 lanes call it; returns the half's answer in each of its lanes.
-__device__ __forceinline__ uint32_t dl_owner_wave(const uint32_t *__restrict__ P, uint32_t k, uint32_t b, uint32_t lane) {
-    uint32_t lo = 0, hi = k;
-    while (__ballot(lo < hi) != 0) {
-        const uint32_t step = max((hi - lo + 31) / 32, 1u);
-        const uint32_t idx = lo + ((lane & 31u) + 1) * step;  // <= 2^20 + 2^20 + 32
-        const bool le = idx <= hi && P[idx] <= b;             // P is monotone: true in a prefix of the half
-        const uint64_t bal = __ballot(le);
-        const uint32_t c = __popc(lane < 32 ? uint32_t(bal) : uint32_t(bal >> 32));
-        lo += c * step;
-        hi = min(hi, lo + step - 1);
-    }
-    return lo;
-}
-
 // Delivered bytes [b0, b1), b1 - b0 <= 16, as bytes [skip, skip + b1 - b0) of a vector, piece
 // by piece: a piece is what one record gives to the vector.  Each piece comes from one
 // widened load of the 16 source bytes that put it at its place in the vector (the bytes
@@ -266,7 +236,7 @@ k_deliver_copy(const uint8_t *__restrict__ img, uint32_t img_bytes, uint32_t vec
         // the records this round's bytes come from: between the owners of its first and last byte
         const uint32_t fb = 16 * v0 > ph ? 16 * v0 - ph : 0u;
         const uint32_t lb = min(16 * (v0 + kDlRound) - ph, total) - 1;  // 16 * (v0 + 256) <= 2^31 + 4 KiB
-        const uint32_t edge = dl_owner_wave(P, k, lane < 32 ? fb : lb, lane);
+        const uint32_t edge = owner_wave(P, k, lane < 32 ? fb : lb, lane);
         const uint32_t olo = __shfl(edge, 0, 64), ohi = __shfl(edge, 63, 64);
         // their prefix sums P[olo .. ohi + 1] in LDS, if they fit (a round of 4 KiB holds 30 Zipf records)
         const uint32_t cnt = ohi - olo + 2;
@@ -288,7 +258,7 @@ k_deliver_copy(const uint8_t *__restrict__ img, uint32_t img_bytes, uint32_t vec
             soff[u] = 0;
             fast[u] = false;
             if (b0[u] < b1[u]) {
-                own[u] = dl_owner(p, olo, ohi, b0[u]);
+                own[u] = owner(p, olo, ohi, b0[u]);
                 const uint32_t x = own[u] * WTP_MAX_PAYLOAD + (b0[u] - p(own[u]));
                 sh[u] = x & 3u;
                 soff[u] = x - sh[u];

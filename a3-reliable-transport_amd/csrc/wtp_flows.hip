@@ -30,8 +30,9 @@
 //                              compaction of k_ack_emit) and stores the ACKs; the cumulative
 //                              seqNum is the flow's ACK after the whole batch, flow_ack[f].
 //
-// The kernels keep their own bodies; nothing here is shared with
-// wtp_accept.hip or wtp_ack.hip beyond wtp_common.hpp.
+// From wtp_common.hpp, with wtp_accept.hip and wtp_ack.hip: the claim constant, ack_lower, the
+// 16-lane slot copy (copy_slot16) and the ACK datagram's store (store_ack).  The ordered
+// compaction keeps its own body here as there.
 // A separate translation unit: see wtp_common.hpp.
 #include <algorithm>
 
@@ -40,9 +41,6 @@
 namespace wtp {
 namespace dev {
 
-constexpr uint32_t kFlowClaim = 0x80000000u;  // claim of datagram i = kFlowClaim | i (n < 2^31)
-constexpr uint32_t kFlowGroup = 16;           // lanes per datagram in k_flows_place
-constexpr uint32_t kFlowVecs = (WTP_MAX_PAYLOAD / 16 + kFlowGroup - 1) / kFlowGroup;  // 91 vectors -> 6 per lane
 constexpr uint32_t kFlowBlock = 1024;         // datagrams per block of the ACK kernels
 constexpr uint32_t kFlowWaves = kFlowBlock / 64;
 constexpr uint32_t kFlowCounts = WTP_RX_MAX_BATCH / kFlowBlock / kFlowBlock;  // block counts per lane of k_flows_ack_emit
@@ -68,16 +66,6 @@ __device__ __forceinline__ uint32_t flow_slot(const uint8_t *__restrict__ ring, 
     return len <= WTP_MAX_PAYLOAD && type == WTP_TYPE_DATA && s < window ? f * window + s : WTP_NOT_PLACED;
 }
 
-// ack[f] is kept as seq0 + (lowest EMPTY slot seen so far); "lower" is taken on the slot index.
-__device__ __forceinline__ void flow_ack_lower(uint32_t *ack, uint32_t seq0, uint32_t s) {
-    uint32_t cur = __hip_atomic_load(ack, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (s < cur - seq0) {
-        const uint32_t seen = atomicCAS(ack, cur, seq0 + s);
-        if (seen == cur) break;
-        cur = seen;
-    }
-}
-
 __global__ void __launch_bounds__(256)
 k_flows_claim(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t *__restrict__ recv_len,
               const uint8_t *__restrict__ ok, const uint32_t *__restrict__ flow, uint64_t n,
@@ -87,7 +75,7 @@ k_flows_claim(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t 
     if (i >= n) return;
     uint32_t s = 0, len = 0;
     const uint32_t g = flow_slot(ring, stride, recv_len, ok, flow, i, seq0, nflows, window, s, len);
-    if (g != WTP_NOT_PLACED) atomicMin(&slot_len[g], kFlowClaim | uint32_t(i));
+    if (g != WTP_NOT_PLACED) atomicMin(&slot_len[g], kClaim | uint32_t(i));
 }
 
 __global__ void __launch_bounds__(256)
@@ -114,51 +102,26 @@ k_flows_place(const uint8_t *__restrict__ ring, uint64_t stride, const uint32_t 
                 const uint32_t f = g / window, s = g - f * window;
                 const uint32_t first = lane - min(s, lane);
                 const uint64_t mine = (m >> first) << first;           // lanes first .. 63
-                if ((mine & ((uint64_t(1) << lane) - 1)) == 0) flow_ack_lower(&ack[f], seq0[f], s);
+                if ((mine & ((uint64_t(1) << lane) - 1)) == 0) ack_lower(&ack[f], seq0[f], s);
             }
         }
     }
-    const uint64_t i = t / kFlowGroup;
-    const uint32_t g = uint32_t(t % kFlowGroup);
+    const uint64_t i = t / kGroup;
+    const uint32_t g = uint32_t(t % kGroup);
     if (i >= n) return;
     uint32_t s = 0, len = 0;
     uint32_t gs = flow_slot(ring, stride, recv_len, ok, flow, i, seq0, nflows, window, s, len);
     // the owner's claim is still in the slot: only this group publishes over it, and it
     // does so after this load (the 16 lanes of a group share a wave)
-    if (gs != WTP_NOT_PLACED && slot_len[gs] != (kFlowClaim | uint32_t(i))) gs = WTP_NOT_PLACED;
+    if (gs != WTP_NOT_PLACED && slot_len[gs] != (kClaim | uint32_t(i))) gs = WTP_NOT_PLACED;
     if (gs == WTP_NOT_PLACED) {
         if (place && g == 0) place[i] = WTP_NOT_PLACED;
         return;
     }
     const uint8_t *src = ring + i * stride + WTP_HEADER_BYTES;
     uint8_t *dst = out + uint64_t(gs) * WTP_MAX_PAYLOAD;
-    if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0) {
-        const u32x4 *vs = reinterpret_cast<const u32x4 *>(src);
-        u32x4 *vd = reinterpret_cast<u32x4 *>(dst);
-        const uint32_t nvec = len / 16;
-        if (len == WTP_MAX_PAYLOAD) {
-            // a full packet, 91 vectors: rows 0 .. 4 whole, row 5 lanes 0 .. 10; all of a
-            // lane's loads are in flight before its first store
-            u32x4 w[kFlowVecs];
-#pragma unroll
-            for (uint32_t k = 0; k + 1 < kFlowVecs; ++k) w[k] = __builtin_nontemporal_load(vs + g + k * kFlowGroup);
-            const bool last = g + (kFlowVecs - 1) * kFlowGroup < WTP_MAX_PAYLOAD / 16;
-            if (last) w[kFlowVecs - 1] = __builtin_nontemporal_load(vs + g + (kFlowVecs - 1) * kFlowGroup);
-#pragma unroll
-            for (uint32_t k = 0; k + 1 < kFlowVecs; ++k) __builtin_nontemporal_store(w[k], vd + g + k * kFlowGroup);
-            if (last) __builtin_nontemporal_store(w[kFlowVecs - 1], vd + g + (kFlowVecs - 1) * kFlowGroup);
-        } else {
-#pragma clang loop unroll_count(2)
-            for (uint32_t v = g; v < nvec; v += kFlowGroup)
-                __builtin_nontemporal_store(__builtin_nontemporal_load(vs + v), vd + v);
-        }
-        const uint32_t b = nvec * 16 + g;  // byte-exact tail: at most 15 bytes, one per lane
-        if (b < len) dst[b] = src[b];
-    } else {
-        // any other alignment: bytes (exact; no access wider than the buffers' alignment)
-#pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
-        for (uint32_t b = g; b < len; b += kFlowGroup) dst[b] = src[b];
-    }
+    const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0;
+    copy_slot16<true, true>(src, dst, len, g, vec);
     if (g == 0) {
         slot_len[gs] = len;
         if (place) place[i] = s;  // the slot within the flow
@@ -241,19 +204,7 @@ k_flows_ack_emit(const uint8_t *__restrict__ ring, uint64_t stride, const uint32
     if (!ans || rank < skip || rank - skip >= max_acks) return;
     const uint32_t k = rank - skip;
     if (mode == WTP_ACK_CUMULATIVE) seq = flow_ack[f];  // the flow's ACK after the whole batch
-    // htonl{type = 3, seqNum, length = 0, checksum = crc32("") = 0}
-    uint8_t *slot = wire + uint64_t(k) * ack_stride;
-    if ((reinterpret_cast<uintptr_t>(slot) & 15u) == 0) {  // one 16-B store
-        *reinterpret_cast<u32x4 *>(slot) = header_be(WTP_TYPE_ACK, seq, 0u, 0u);
-    } else {
-        // any other alignment: bytes (no access wider than the slot's alignment)
-        // the loop stays rolled, or the compiler merges the sixteen stores into one
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-        for (uint32_t b = 0; b < WTP_HEADER_BYTES; ++b) {
-            const uint32_t word = b < 4 ? uint32_t(WTP_TYPE_ACK) : b < 8 ? seq : 0u;
-            slot[b] = uint8_t(word >> (8 * (3 - b % 4)));
-        }
-    }
+    store_ack(wire + uint64_t(k) * ack_stride, seq);
     if (src) src[k] = i;
 }
 
@@ -312,7 +263,7 @@ extern "C" int wtp_accept_data_packets_flows(const void *d_dgrams, size_t stride
     }
     // one 16-lane group per datagram; at least enough lanes to scan a small state at once
     const uint64_t scan = d_ack ? std::min<uint64_t>((slots + 255) / 256, 1024) : 0;
-    const uint64_t blocks = std::max<uint64_t>({1, (uint64_t(n) * dev::kFlowGroup + 255) / 256, scan});
+    const uint64_t blocks = std::max<uint64_t>({1, (uint64_t(n) * dev::kGroup + 255) / 256, scan});
     return launch("k_flows_place", dev::k_flows_place, dim3(unsigned(blocks)), dim3(256), st, ring, uint64_t(stride),
                   d_recv_len, d_ok, d_flow, uint64_t(n), d_seq0, nflows, window, static_cast<uint8_t *>(d_out), d_slot_len,
                   d_place, d_ack);

@@ -46,8 +46,9 @@
 // Every word of d_work that a kernel reads was written by an earlier launch of the same
 // call; the calls keep no state and read no library table.
 //
-// The kernels keep their own bodies; nothing here is shared with
-// wtp_deliver.hip or wtp_advance.hip beyond wtp_common.hpp.
+// From wtp_common.hpp, with wtp_deliver.hip: the two owner searches (owner, owner_wave).  The
+// kernels keep their own bodies, k_rx_advance_flows its copy of copy_slot16's text: on the
+// helper its machine code changed and the timing rule did not let it move.
 // A separate translation unit: see wtp_common.hpp.
 #include <algorithm>
 
@@ -69,9 +70,6 @@ constexpr uint32_t kFfRound = 64 * kFfVecs;  // vectors per wave and round (4 Ki
 constexpr uint32_t kFfMaxBlocks = 2048;  // the capped grid of the copy and of the advance
 constexpr uint32_t kFfStage = 256;       // records a wave keeps in LDS per round
 
-constexpr uint32_t kFfGroup = 16;  // lanes per slot in k_rx_advance_flows
-constexpr uint32_t kFfAdvVecs = (WTP_MAX_PAYLOAD / 16 + kFfGroup - 1) / kFfGroup;  // 91 vectors -> 6 per lane
-static_assert(WTP_MAX_PAYLOAD % 16 == 0, "every slot of a 16-B aligned image is 16-B aligned");
 static_assert(uint64_t(WTP_RX_MAX_FLOW_SLOTS) + WTP_RX_MAX_WINDOW < (uint64_t(1) << 32), "a source slot fits 32 bits");
 
 __device__ __forceinline__ uint64_t ff_min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
@@ -301,36 +299,6 @@ k_dflows_out(uint32_t nflows, uint32_t max_slots, uint64_t stream_off, const uin
     info[4 * uint64_t(f) + 3] = Q[end > R ? end : R] - Q[R];
 }
 
-// The last index in [lo, hi] whose p is <= b (p(lo) <= b is the caller's).
-template <class Get>
-__device__ __forceinline__ uint32_t ff_owner(Get p, uint32_t lo, uint32_t hi, uint32_t b) {
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (p(mid) <= b)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
-// The same over Q[0 .. k] by a half-wave at a time: lanes 0 .. 31 look for one byte, lanes 32 ..
-// 63 for another, 32 probes per step, so 2^24 entries take five dependent loads.  All 64 lanes
-// call it; returns the half's answer in each of its lanes.
-__device__ __forceinline__ uint32_t ff_owner_wave(const uint64_t *__restrict__ Q, uint32_t k, uint64_t b, uint32_t lane) {
-    uint32_t lo = 0, hi = k;
-    while (__ballot(lo < hi) != 0) {
-        const uint32_t step = max((hi - lo + 31) / 32, 1u);
-        const uint32_t idx = lo + ((lane & 31u) + 1) * step;  // <= 2^24 + 2^24 + 32
-        const bool le = idx <= hi && Q[idx] <= b;             // Q is monotone: true in a prefix of the half
-        const uint64_t bal = __ballot(le);
-        const uint32_t c = __popc(lane < 32 ? uint32_t(bal) : uint32_t(bal >> 32));
-        lo += c * step;
-        hi = min(hi, lo + step - 1);
-    }
-    return lo;
-}
-
 // Delivered bytes [b0, b1) of the round (relative to its first record's Q), b1 - b0 <= 16, as
 // bytes [skip, skip + b1 - b0) of a vector, piece by piece: a piece is what one record gives to
 // the vector, from one widened load of the 16 source bytes that put it at its place (the bytes
@@ -397,7 +365,7 @@ k_dflows_copy(const uint8_t *__restrict__ img, uint64_t img_bytes, uint32_t vec,
         // the records this round's bytes come from: between the owners of its first and last byte
         const uint64_t fb = 16 * uint64_t(v0) > ph ? 16 * uint64_t(v0) - ph : 0u;
         const uint64_t lb = ff_min64(16 * (uint64_t(v0) + kFfRound) - ph, total) - 1;
-        const uint32_t edge = ff_owner_wave(Q, K, lane < 32 ? fb : lb, lane);
+        const uint32_t edge = owner_wave(Q, K, lane < 32 ? fb : lb, lane);
         const uint32_t olo = __shfl(edge, 0, 64), ohi = __shfl(edge, 63, 64);
         // everything below is relative to the first record's Q: the round's bytes and the
         // records' ends are within 4 KiB + 1456 of it
@@ -428,7 +396,7 @@ k_dflows_copy(const uint8_t *__restrict__ img, uint64_t img_bytes, uint32_t vec,
             soff[u] = 0;
             fast[u] = false;
             if (any) {
-                own[u] = ff_owner(p, olo, ohi, b0[u]);
+                own[u] = owner(p, olo, ohi, b0[u]);
                 const uint64_t x = uint64_t(m(own[u])) * WTP_MAX_PAYLOAD + (b0[u] - p(own[u]));
                 sh[u] = uint32_t(x) & 3u;
                 soff[u] = x - sh[u];
@@ -498,7 +466,7 @@ __global__ void __launch_bounds__(256, 8)
 k_rx_advance_flows(const uint8_t *__restrict__ img, const uint32_t *__restrict__ slot_len, uint32_t slots, uint32_t window,
                    const uint64_t *__restrict__ flow_adv, const uint32_t *__restrict__ seq0, uint8_t *__restrict__ img_next,
                    uint32_t *__restrict__ slot_len_next, uint32_t *__restrict__ seq0_next, uint32_t vec) {
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x / 64, g = lane % kFfGroup, q = lane / kFfGroup;
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x / 64, g = lane % kGroup, q = lane / kGroup;
     const uint32_t rounds = (slots + 63) / 64, step = gridDim.x * 4;
     for (uint32_t r = blockIdx.x * 4 + wv; r < rounds; r += step) {
         const uint32_t gs = r * 64 + lane;
@@ -516,7 +484,7 @@ k_rx_advance_flows(const uint8_t *__restrict__ img, const uint32_t *__restrict__
         while (todo) {
             uint32_t pick = 64;
 #pragma unroll
-            for (uint32_t j = 0; j < 64 / kFfGroup; ++j) {
+            for (uint32_t j = 0; j < 64 / kGroup; ++j) {
                 const uint32_t b = todo ? uint32_t(__builtin_ctzll(todo)) : 64u;
                 todo &= todo - 1;
                 if (q == j) pick = b;
@@ -534,25 +502,25 @@ k_rx_advance_flows(const uint8_t *__restrict__ img, const uint32_t *__restrict__
                 if (len == WTP_MAX_PAYLOAD) {
                     // a full slot, 91 vectors: rows 0 .. 4 whole, row 5 lanes 0 .. 10; all of a
                     // lane's loads are in flight before its first store
-                    u32x4 w[kFfAdvVecs];
+                    u32x4 w[kSlotVecs];
 #pragma unroll
-                    for (uint32_t k = 0; k + 1 < kFfAdvVecs; ++k) w[k] = vs[g + k * kFfGroup];
-                    const bool last = g + (kFfAdvVecs - 1) * kFfGroup < WTP_MAX_PAYLOAD / 16;
-                    if (last) w[kFfAdvVecs - 1] = vs[g + (kFfAdvVecs - 1) * kFfGroup];
+                    for (uint32_t k = 0; k + 1 < kSlotVecs; ++k) w[k] = vs[g + k * kGroup];
+                    const bool last = g + (kSlotVecs - 1) * kGroup < WTP_MAX_PAYLOAD / 16;
+                    if (last) w[kSlotVecs - 1] = vs[g + (kSlotVecs - 1) * kGroup];
 #pragma unroll
-                    for (uint32_t k = 0; k + 1 < kFfAdvVecs; ++k) vd[g + k * kFfGroup] = w[k];
-                    if (last) vd[g + (kFfAdvVecs - 1) * kFfGroup] = w[kFfAdvVecs - 1];
+                    for (uint32_t k = 0; k + 1 < kSlotVecs; ++k) vd[g + k * kGroup] = w[k];
+                    if (last) vd[g + (kSlotVecs - 1) * kGroup] = w[kSlotVecs - 1];
                 } else {
                     // a shorter one: a Zipf record is a vector or two per lane
 #pragma clang loop unroll_count(2)
-                    for (uint32_t x = g; x < nvec; x += kFfGroup) vd[x] = vs[x];
+                    for (uint32_t x = g; x < nvec; x += kGroup) vd[x] = vs[x];
                 }
                 const uint32_t b = nvec * 16 + g;  // byte-exact tail: at most 15 bytes, one per lane
                 if (b < len) dst[b] = src[b];
             } else {
                 // any other alignment: bytes (exact; no access wider than the images' alignment)
 #pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
-                for (uint32_t b = g; b < len; b += kFfGroup) dst[b] = src[b];
+                for (uint32_t b = g; b < len; b += kGroup) dst[b] = src[b];
             }
         }
     }

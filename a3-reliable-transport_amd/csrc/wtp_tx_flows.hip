@@ -42,7 +42,9 @@
 //                           below nrec), seqNum seq0[f] + s.
 //
 // Its own copies of the bodies, not templates shared with wtp_tx.hip and wtp_txvar.hip: the
-// existing kernels keep their machine code.
+// existing kernels keep their machine code.  The emit body as one
+// function template for k_tx_emit_var and k_txf_emit changed both kernels' code and did not
+// stay within the parent's spread on every row of tools/tx_flows_bench.py.
 // A separate translation unit: see wtp_common.hpp.
 #include <algorithm>
 
