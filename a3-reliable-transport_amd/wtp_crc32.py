@@ -93,6 +93,8 @@ def _load() -> tuple:
         "wtp_conn_scratch_bytes": (sz, [sz, u32]),
         "wtp_flows_control": (i32, [vp, sz, vp, vp, sz, vp, vp, sz, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, sz, u32, vp, vp,
                                     vp, vp, vp, vp, vp, sz, vp]),
+        "wtp_rx_digest_scratch_bytes": (sz, [u32]),
+        "wtp_rx_digest_flows": (i32, [vp, sz, vp, u32, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, sz, vp]),
         "wtp_crc32_combine": (u32, [u32, u32, u64]),
         "wtp_crc32_concat_work_bytes": (sz, [sz]),
         "wtp_crc32_concat": (i32, [vp, vp, u64, u64, sz, vp, sz, vp, vp]),
@@ -450,6 +452,32 @@ def flows_control(dgrams, stride: int, recv_len, keys, key_stride: int, flow, ok
                                  _dptr(free), _dptr(free_pos), _dptr(ack_wire), ack_stride, max_acks, _dptr(ack_src),
                                  _dptr(opened), _dptr(opened_src), _dptr(closed), _dptr(verdict), _dptr(counts), wp, wb,
                                  _stream(stream)), "wtp_flows_control")
+
+
+# ---- the running whole-file CRC-32 of every connection -----------------------------------
+def rx_digest_scratch_bytes(nflows: int) -> int:
+    """The scratch of rx_digest_flows (wtp_rx_digest_scratch_bytes): 16432 + 12 * nflows."""
+    return int(LIB.wtp_rx_digest_scratch_bytes(nflows))
+
+
+def rx_digest_flows(stream_buf, stream_bytes: int, flow_info, nflows: int, flow_crc, flow_bytes, reset, reset_count,
+                    max_reset: int, report, report_count, max_report: int, report_crc, report_bytes, counts, work=None,
+                    stream=None) -> None:
+    """Folds what rx_deliver_flows delivered into every flow's running CRC-32 and byte count
+    (wtp_rx_digest_flows): flow_info is rx_deliver_flows' (nflows x 4 x u64) as it is, flow f's
+    bytes are stream_buf[info[f][2] .. + info[f][3]); flow_crc (nflows x u32) and flow_bytes
+    (nflows x u64) are the caller's state, zeroed once, updated in place with zlib's combine.
+    Then the flows of `report` (u32 ids; report_count: one device u32, at most max_report are
+    used) are gathered into report_crc / report_bytes, and then the flows of `reset` are zeroed;
+    with flows_control's `closed` / counts[3:] and `opened` / counts[2:] a closed connection's
+    entry is its whole file's CRC and a reused id starts from zero.  Either list may be None
+    (with its count).  counts (4 x u64) = (bytes folded, flows folded, ranges refused, reports
+    written)."""
+    work, wp, wb = _work(work, rx_digest_scratch_bytes(nflows))
+    _check(LIB.wtp_rx_digest_flows(_dptr(stream_buf), stream_bytes, _dptr(flow_info), nflows, _dptr(flow_crc),
+                                   _dptr(flow_bytes), _dptr(reset), _dptr(reset_count), max_reset, _dptr(report),
+                                   _dptr(report_count), max_report, _dptr(report_crc), _dptr(report_bytes), _dptr(counts),
+                                   wp, wb, _stream(stream)), "wtp_rx_digest_flows")
 
 
 def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:

@@ -1044,6 +1044,84 @@ int wtp_flows_control(const void *d_dgrams, size_t stride, const uint32_t *d_rec
                       uint32_t *d_verdict, uint32_t *d_counts,
                       void *d_work, size_t work_bytes, void *stream);
 
+/* ---- the running whole-file CRC-32 of every connection --------------------------------
+   wtp_rx_digest_flows keeps, per flow, the CRC-32 and the byte count of everything delivered
+   for the flow so far, in caller-owned device memory: what wtp_crc32_buffer gives for one
+   transfer, for any number of connections in a fixed number of launches.  It is the seventh
+   call of the receive round, classify -> accept_flows -> build_acks_flows -> deliver_flows ->
+   advance_flows -> control -> digest, on the same stream and in the same captured graph.
+
+   Inputs and state.  d_stream[0 .. stream_bytes) is wtp_rx_deliver_flows' stream and
+   d_flow_info its output, passed as it is: d_flow_info[4f+2] = B_f, the absolute stream offset
+   of the flow's first delivered byte, and d_flow_info[4f+3] = bytes_f; words 4f+0 and 4f+1 are
+   not read.  All values are read on the device when the kernels run.  The state is
+   d_flow_crc[nflows] and d_flow_bytes[nflows], caller-owned, updated in place; zero means
+   "nothing yet" (the CRC of the empty message is 0), so the caller zeroes both once.
+
+   The fold, stated sequentially for every f < nflows.  The range is valid iff B_f <=
+   stream_bytes and bytes_f <= stream_bytes - B_f (wtp_build_data_packets_var's rule, in 64
+   bits, no overflow).  A valid flow with bytes_f > 0: d_flow_crc[f] = combine(d_flow_crc[f],
+   crc32(d_stream[B_f .. B_f + bytes_f)), bytes_f), zlib semantics, bit-identical to
+   wtp_crc32_combine, and d_flow_bytes[f] += bytes_f (mod 2^64).  A valid flow with bytes_f ==
+   0 and an invalid flow leave both words as they were; the invalid one is counted and no
+   status flag is set (as in wtp_tx_ingest_acks).  The ranges of different flows may overlap
+   and come in any order: each flow is folded on its own, so every input is defined.  No byte
+   outside [d_stream, d_stream + stream_bytes) is loaded, the aligned 16-B vector loads
+   included: a vector that crosses an edge of the buffer is loaded bytewise, as in the builder.
+
+   Report, then reset, both after the fold and in this order.  Report: for q < min(
+   *d_report_count, max_report) with g = d_report[q]: d_report_crc[q] = d_flow_crc[g] and
+   d_report_bytes[q] = d_flow_bytes[g]; g >= nflows writes 0 and 0xFFFFFFFFFFFFFFFF.  Entries
+   past the count stay as they were.  Reset: for j < min(*d_reset_count, max_reset) with g =
+   d_reset[j] < nflows: d_flow_crc[g] = 0 and d_flow_bytes[g] = 0; duplicates and ids >= nflows
+   are harmless.  A flow in both lists is reported with its folded value and then zeroed.
+   Either list may be absent: both of its pointers NULL.  The intended wiring, after
+   wtp_flows_control on the same stream: d_report = d_closed and d_report_count = control's
+   d_counts + 3; d_reset = d_opened and d_reset_count = control's d_counts + 2.  That is exact:
+   control refuses to close a flow whose slot 0 is still filled (WTP_CTL_END_BUSY), so at the
+   end of the round in which a flow closes everything of its file has been delivered and
+   folded; and an id freed in a call serves no open of that call, so an id that is reused is
+   zeroed at the end of the round that opened it, before the next round delivers its first
+   data.  A caller without a connection table calls this right after deliver with both lists
+   NULL.
+
+   d_counts[0 .. 4) (64-bit) = {bytes folded, flows folded, ranges refused, reports written},
+   always written, also for nflows == 0, which is valid.  Nothing else is written: d_stream and
+   every other input are only read, and the memory behind every output array is untouched.
+   Consequence: with nflows == 1, a zeroed state and any sequence of rounds, d_flow_crc[0]
+   equals wtp_crc32_buffer over the concatenation of everything delivered.
+
+   d_work is the caller's scratch (any alignment, contents arbitrary on entry, unspecified on
+   return; every word the call reads it has written before).  wtp_rx_digest_scratch_bytes(
+   nflows) = 16432 + 12*nflows (its argument clamped to WTP_RX_MAX_FLOWS), monotone and at most
+   64 KiB + 16 bytes per flow.
+   WTP_EINVAL (before any device is touched, each with its own message): nflows >
+   WTP_RX_MAX_FLOWS; work_bytes below the size above; a NULL d_counts or d_work; with nflows >
+   0 a NULL d_flow_info, d_flow_crc or d_flow_bytes, or a NULL d_stream with stream_bytes > 0;
+   exactly one of d_reset and d_reset_count NULL; exactly one of d_report and d_report_count
+   NULL; a report list with max_report > 0 and a NULL d_report_crc or d_report_bytes.
+   Stream-ordered launches (unit counts, their scan, the hash, the merge of its records, the
+   fold, the report, the reset) with no host synchronisation, no allocation and no library
+   table: the hash uses its unit's own compile-time tables, so no wtp_init is needed before a
+   capture.  Grids are sized from nflows, stream_bytes and the list capacities (the hash runs
+   on a capped persistent grid), never from device values, and the number of launches does
+   not depend on nflows.  Nothing is serial per flow: the delivered ranges are cut into 4-KiB
+   units that spread over the grid flow-major, so 2^20 flows of one short record, 2^16 flows
+   that are mostly empty and one flow of 2^20 slots are the same kind of work, and the atomic
+   updates of one flow's word stay below the waves of one workgroup whatever its size.  Graph
+   captures, replays and concurrent calls on different states and work buffers are
+   independent.  Fast path: every 16-B vector inside the buffer, at any byte phase of d_stream
+   and of B_f.  wtp_last_kernel() names "k_dig_reset", or "k_dig_report" when no reset list is
+   given, max_reset == 0 or nflows == 0. */
+size_t wtp_rx_digest_scratch_bytes(uint32_t nflows);
+int wtp_rx_digest_flows(const void *d_stream, size_t stream_bytes,
+                        const uint64_t *d_flow_info, uint32_t nflows,
+                        uint32_t *d_flow_crc, uint64_t *d_flow_bytes,
+                        const uint32_t *d_reset, const uint32_t *d_reset_count, uint32_t max_reset,
+                        const uint32_t *d_report, const uint32_t *d_report_count, uint32_t max_report,
+                        uint32_t *d_report_crc, uint64_t *d_report_bytes,
+                        uint64_t *d_counts, void *d_work, size_t work_bytes, void *stream);
+
 /* ---- whole-buffer CRC: the fold of payload CRCs ------------------------------------
    The reference's crc32(buf, size) takes any size; these give it for device-resident data
    of any size from the per-chunk CRCs, by zlib's crc32_combine identity
